@@ -27,8 +27,8 @@ mkdir -p $O
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0 XMPI_TIMEOUT_S=${XMPI_TIMEOUT_S:-120}
 BIN=$ROOT/mpi_amd/bin
 REH=${XMPI_8GPU_REHEARSAL:-0}
-if [ "$REH" = 1 ]; then L=131072; M=65536; S=16384; C5=1048576; C3=16384; K="2 1"; KS="2 1"; CS="65536 2"; BARGS="--steps 2 --warmup 1 --size-mib 0.25 --no-cpu --no-probe"
-else L=268435456; M=16777216; S=1048576; C5=1073741824; C3=2097152; K="20 5"; KS="200 10"; CS="1048576 200"; BARGS="--steps 20 --warmup 5"; fi
+if [ "$REH" = 1 ]; then L=131072; M=65536; S=16384; C5=1048576; C3=16384; K="2 1"; KS="2 1"; CS="65536 2"; BARGS="--full --steps 2 --warmup 1 --size-mib 0.25 --no-cpu --no-probe"
+else L=268435456; M=16777216; S=1048576; C5=1073741824; C3=2097152; K="20 5"; KS="200 10"; CS="1048576 200"; BARGS="--full --steps 20 --warmup 5"; fi
 cd $ROOT
 if [ "$REH" != 1 ]; then
 timeout 1200 python -m pytest tests/test_gpu_collectives.py -k "split_form or stepped or ll_" -x -q > $O/pytest_split_sched_ll.log 2>&1; echo "pytest rc=$?"

@@ -7,7 +7,7 @@ BIN=mpi_amd/bin
 port=7100
 for i in 1 2 3; do
   for col in 1 0; do
-    XMPI_HEAP_COLOUR=$col timeout 120 python bench.py --algo zcopy --no-extras --no-cpu --no-production > $O/n1_c${col}_$i.json 2>> $O/err.txt
+    XMPI_HEAP_COLOUR=$col timeout 120 python bench.py --full --algo zcopy --no-extras --no-cpu --no-production > $O/n1_c${col}_$i.json 2>> $O/err.txt
     port=$((port + 13))
     XMPI_HEAP_COLOUR=$col XMPI_BASEPORT=$port timeout 120 $BIN/xmpirun 8 $BIN/allreduce_bench $((256<<20)) 20 5 split fused ring > $O/p8_c${col}_$i.json 2>> $O/err.txt
   done

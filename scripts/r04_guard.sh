@@ -24,7 +24,7 @@ for CAP in 32 64 128 256 512 1024; do
   XMPI_P2P_GRID_CAP=$CAP XMPI_BASEPORT=$port timeout 100 $BIN/xmpirun 2 $BIN/allreduce_bench 16777216 5 2 fused > $O/bounce_cap$CAP.json 2> $O/bounce_cap$CAP.err
 done
 cd /tmp
-B="python $GRAFT_REPO_ROOT/bench.py --algo zcopy --no-extras --no-cpu --no-production"
+B="python $BIN/../../bench.py --full --algo zcopy --no-extras --no-cpu --no-production"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_n1 -- $B > $O/bench_zcopy_under_rocprof.json 2> $O/trace_n1.err
 XMPI_BASEPORT=7900 timeout 200 rocprofv3 --marker-trace --kernel-trace --output-format csv -d $O/markers -- $BIN/xmpirun 2 $BIN/coll_sweep 1048576 20 > $O/coll_sweep_markers.json 2> $O/markers.err
 echo "marker trace rc=$?"

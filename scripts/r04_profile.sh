@@ -16,10 +16,10 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 O=$GRAFT_REPO_ROOT/gpurun_out/r04
 rm -rf $O; mkdir -p $O
 BIN=$GRAFT_REPO_ROOT/mpi_amd/bin
-timeout 600 python bench.py > $O/bench_n1_default.json 2> $O/bench_n1_default.err
+timeout 600 python bench.py --full > $O/bench_n1_default.json 2> $O/bench_n1_default.err
 cp bench_extras.json $O/bench_n1_default_extras.json
 tail -c 400 $O/bench_n1_default.err
-B="python $GRAFT_REPO_ROOT/bench.py --algo zcopy --no-extras --no-cpu --no-production"
+B="python $BIN/../../bench.py --full --algo zcopy --no-extras --no-cpu --no-production"
 PROD="$BIN/xmpirun 8 $BIN/allreduce_bench 268435456 20 5"
 export XMPI_TIMEOUT_S=40 XMPI_NGPUS=1
 cd /tmp

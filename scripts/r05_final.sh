@@ -10,9 +10,9 @@ BIN=$GRAFT_REPO_ROOT/mpi_amd/bin
 (time timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -25) > $O/gpusuite.log 2>&1
 tail -6 $O/gpusuite.log
 timeout 120 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cp bench_extras.json $O/bench_n1_extras.json
-B="python $GRAFT_REPO_ROOT/bench.py --algo zcopy --no-extras --no-cpu --no-production"
+B="python $BIN/../../bench.py --full --algo zcopy --no-extras --no-cpu --no-production"
 export XMPI_TIMEOUT_S=40 XMPI_NGPUS=1
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_n1 -- $B > $O/bench_zcopy_under_rocprof.json 2> $O/stats_n1.err

@@ -14,10 +14,10 @@ BIN=$GRAFT_REPO_ROOT/mpi_amd/bin
 (time timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -25) > $O/gpusuite.log 2>&1
 tail -6 $O/gpusuite.log
 timeout 120 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cp bench_extras.json $O/bench_n1_extras.json
 export XMPI_TIMEOUT_S=40 XMPI_NGPUS=1
-B="python $GRAFT_REPO_ROOT/bench.py --algo zcopy --no-extras --no-cpu --no-production"
+B="python $BIN/../../bench.py --full --algo zcopy --no-extras --no-cpu --no-production"
 PROD="$BIN/xmpirun 8 $BIN/allreduce_bench 268435456 20 5"
 PRODS="$BIN/xmpirun 8 $BIN/allreduce_bench 268435456 5 2"
 cd /tmp

@@ -25,7 +25,7 @@ for m in ring ring_push; do
   XMPI_BASEPORT=7200 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_prod_$m -- $PROD $m > $O/prod_${m}_under_rocprof.json 2> $O/stats_prod_$m.err
 done
 cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cp bench_extras.json $O/bench_n1_extras.json
 find $O -name "*.csv" ! -name "*kernel_stats.csv" -delete; find $O -name "*.db" -delete
 cut -c1-300 $O/bench_n1.json; echo; python - <<'PY'

@@ -9,7 +9,7 @@ BIN=$GRAFT_REPO_ROOT/mpi_amd/bin
 (time timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -25) > $O/gpusuite.log 2>&1
 tail -6 $O/gpusuite.log
 timeout 120 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cp bench_extras.json $O/bench_n1_extras.json
 cut -c1-600 $O/bench_n1.json; echo
 export XMPI_TIMEOUT_S=40 XMPI_NGPUS=1

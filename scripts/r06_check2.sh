@@ -7,7 +7,7 @@ rm -rf $O; mkdir -p $O
 (time timeout 1500 python -m pytest tests -m gpu -x -q -k "selfcheck or bench_json_contract or bench_extras or degraded or smoke" 2>&1 | tail -15) > $O/pytest.log 2>&1
 tail -6 $O/pytest.log
 timeout 200 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-(time timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err) 2>&1 | grep real
+(time timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err) 2>&1 | grep real
 python - <<'PY'
 import json, os
 O = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/r06_check2"

@@ -16,10 +16,10 @@ if [ -z "$R06_SKIP_SUITE" ]; then
 tail -6 $O/gpusuite.log
 timeout 120 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 fi
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cp bench_extras.json $O/bench_n1_extras.json
 export XMPI_TIMEOUT_S=40 XMPI_NGPUS=1
-B="python $GRAFT_REPO_ROOT/bench.py --algo zcopy --no-extras --no-cpu --no-production"
+B="python $BIN/../../bench.py --full --algo zcopy --no-extras --no-cpu --no-production"
 PRODS="$BIN/xmpirun 8 $BIN/allreduce_bench 268435456 5 2"
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_n1 -- $B > $O/bench_zcopy_under_rocprof.json 2> $O/stats_n1.err

@@ -4,6 +4,7 @@ import argparse
 import importlib.util
 import os
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,3 +113,33 @@ def test_the_quoted_pmc_profile_is_not_stale():
         stem = row["kernel"].split("<")[0]
         assert re.search(r"__global__[^;{]*\b" + re.escape(stem) + r"\s*\(", src), f"{stem}: named by profiles/pmc_traffic.json, not a kernel of mpi_amd/csrc/*.hip"
         assert row["traffic_bytes_per_launch"] > 0 and row["algorithmic_bytes_per_launch"] > 0
+
+
+class _HostBuf:
+    """stands in for a device buffer: download() as mpi_amd.xmpi.DevBuf's, from a host array"""
+
+    def __init__(self, arr):
+        self.raw = arr.view(np.uint8)
+
+    def download(self, dtype, count, byte_offset=0):
+        dt = np.dtype(dtype)
+        return self.raw[byte_offset:byte_offset + count * dt.itemsize].view(dt).copy()
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget():
+    """--dump-outputs: a receive buffer that fits is written whole; a larger one as the elements at a fixed seeded set of indices --
+    the same set on every call -- within the budget for all ranks; as float32 (float64 for 64-bit types), bf16 widened exactly"""
+    m = _bench()
+    from mpi_amd import xmpi
+    small = np.arange(1000, dtype=np.float16)
+    got = m.output_sample(_HostBuf(small), small.size, xmpi.F16, 8)
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = np.random.default_rng(7).random(m.DUMP_BYTES // 4, dtype=np.float32)  # 8 ranks of this would not fit
+    a, b = (m.output_sample(_HostBuf(big), big.size, xmpi.F32, 8) for _ in range(2))
+    assert a.dtype == np.float32 and 0 < a.size <= m.DUMP_BYTES // (8 * 4) and np.array_equal(a, b)
+    assert np.isin(a, big).all() and np.all(np.diff(a) != 0)  # elements of the buffer, no index drawn twice
+    wide = np.arange(m.DUMP_BYTES // 8, dtype=np.int64)
+    w = m.output_sample(_HostBuf(wide), wide.size, xmpi.I64, 8)
+    assert w.dtype == np.float64 and w.size * 8 * 8 <= m.DUMP_BYTES and np.all(np.diff(w) > 0)  # (sorted indices: ascending values)
+    bf = (np.array([1.0, -2.5, 3.140625], dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
+    assert m.output_sample(_HostBuf(bf), 3, xmpi.BF16, 1).tolist() == [1.0, -2.5, 3.140625]

@@ -440,7 +440,7 @@ def test_collective_programs_one_process_per_gpu(stage):
 def test_the_scale_command_on_virtual_gpus(devsim_lib, gpus, tmp_path):
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
     --steps K --warmup W` -- the command the driver runs on an 8-GPU node and no 1-GPU box can (bench.py binds through ctypes:
-    tests/devsim/site/usercustomize.py on PYTHONPATH puts every process of it, the zero-copy probe's children included, on the
+    tests/devsim/site/sitecustomize.py on PYTHONPATH puts every process of it, the zero-copy probe's children included, on the
     stand-in).  A quarter MiB per rank instead of 256: the line's shape and the path, not a rate.  Found this way: every process
     took all ranks to be on ITS device, so an 8-GPU line would have said "intra-HBM" and left the xgmi block out."""
     import json
@@ -449,7 +449,7 @@ def test_the_scale_command_on_virtual_gpus(devsim_lib, gpus, tmp_path):
                XMPI_TIMEOUT_S="60", XMPI_BENCH_EXTRAS_DIR=str(tmp_path))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1",
                         "--master-port", str(29600 + gpus), os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-                        "--size-mib", "0.25", "--no-cpu"], capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
+                        "--size-mib", "0.25", "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 alone prints, one line
@@ -504,8 +504,8 @@ def test_the_scale_command_as_a_lone_process(devsim_lib, gpus, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     # (--no-probe: the child-process probe of every schedule is the torchrun form's test above; here: the lone process' own path)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--size-mib", "0.25", "--no-cpu",
-                        "--no-production", "--no-probe", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--size-mib", "0.25", "--full",
+                        "--no-cpu", "--no-production", "--no-probe", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -521,6 +521,41 @@ def test_the_scale_command_as_a_lone_process(devsim_lib, gpus, tmp_path):
         assert "rejected" not in d["config"]["tuned"]  # (the tuner checked every candidate's answer: nothing wrong on these devices)
     else:
         assert d["config"]["transport"].startswith(f"mixed: 8 ranks on {gpus} GPUs") and d["roofline"]["ranks_per_gpu"] == 8 // gpus
+
+
+def test_the_plain_bench_command_and_its_outputs(devsim_lib, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line and nothing measured or
+    checked beside it (no parity leg, no extras file); DIR holds what every rank's caller received from the last timed step -- the
+    rank-order sum of the seeded inputs, the same on every rank and in a second run"""
+    import json
+    import sys
+
+    import numpy as np
+
+    from oracle import oracle
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tests", "devsim", "site"), XMPI_DEVSIM_LIB=devsim_lib, DEVSIM_DEVICES="1",
+               XMPI_TIMEOUT_S="60", XMPI_BENCH_EXTRAS_DIR=str(tmp_path))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    outs = []
+    for run_no in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size-mib", "0.25",
+                            "--dump-outputs", str(tmp_path / f"out{run_no}")], capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["metric"] == "allreduce_sum_f32_0.25MiB algbw" and d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 3 and d["value"] > 0 and abs(d["value"] - d["config"]["bytes_per_rank"] / d["ms_per_step"] / 1e6) < 1e-6 * d["value"]
+        assert "parity" not in d and "extras_file" not in d and "cpu_baseline" not in d and "roofline_isolated" not in d
+        outs.append([np.load(tmp_path / f"out{run_no}" / f"allreduce_out_rank{g}.npy") for g in range(8)])
+    assert not os.path.exists(tmp_path / "bench_extras.json")
+    count = (1 << 18) // 4
+    want = oracle.reduce_ranks([oracle.fill_range(0, count, oracle.F32, 0, 1000 + q) for q in range(8)], oracle.F32, oracle.SUM)
+    for g in range(8):
+        assert outs[0][g].dtype == np.float32 and outs[0][g].shape == (count,)
+        assert np.array_equal(outs[0][g], outs[1][g]) and np.array_equal(outs[0][g], outs[0][0])
+        assert np.allclose(outs[0][g], want, rtol=0, atol=8e-6), float(np.max(np.abs(outs[0][g] - want)))
 
 
 def test_the_8gpu_script_rehearsal(stage, devsim_lib, tmp_path):

@@ -15,7 +15,7 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--size-mib", "16",
-                        "--no-extras", "--cpu-count", "65536"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-extras", "--cpu-count", "65536"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
     assert len(lines) == 1 and r.stdout.strip().split("\n")[-1] == lines[0]
@@ -70,7 +70,7 @@ def test_bench_extras_tables():
     """the untimed extras at a small size (bench_extras.json): busbw against message size at 1 / 2 / 4 / 8 ranks, cfg 3 at its
     4 ranks, and the one-process-per-rank sweep (ranks meeting on the device)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--size-mib", "16",
-                        "--no-cpu", "--no-production", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu", "--no-production", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")][0]
     assert len(line) < 6000
@@ -106,7 +106,7 @@ def test_bench_multi_process_launch_rehearsal(nproc):
     env = dict(os.environ, XMPI_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--size-mib", "16", "--no-extras", "--no-probe"]
+           "--size-mib", "16", "--full", "--no-extras", "--no-probe"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{\"metric\"")]
@@ -129,7 +129,7 @@ def test_bench_probe_rules_out_a_schedule():
     env = dict(os.environ, XMPI_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", XMPI_BENCH_FAIL_RING="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-           "--size-mib", "16", "--no-extras"]
+           "--size-mib", "16", "--full", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.strip().split("\n") if ln.startswith("{\"metric\"")][0])

@@ -509,9 +509,6 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
 // seed kCheckSeed + r (kernels.hip fill_kernel, pattern 3: signed multiples of 2^-12 below 4 in magnitude: the float32 sum of
 // sixteen of them is exact in EVERY association, so every schedule must produce the same bits) --, compares the receive buffer with
 // the result computed locally (N fills folded with the two-operand kernel: no communication), and votes through the control block.
-const char* const kCandName[xmpi_comm::CAND_COUNT] = {"fold (one kernel)", "fold (one kernel, 2 packets in flight)", "split (meet / body / done)",
-                                                      "push-only", "ring kernel", "halving kernel", "LL lines", "ring kernel, push form",
-                                                      "halving kernel, push form", "tree kernel", "tree kernel, push form"};
 constexpr size_t kSecondPassBytes = (size_t)1 << 20;  // per rank: eight ranks' buffers of that size sit in the L2s (8 x 4 MiB) together from one run to the next
 constexpr long kTuneTimeoutS = 20;  // no-progress limit of a candidate run in a job that otherwise waits for ever
 constexpr uint64_t kCheckSeed = 0x7A11D;
@@ -784,10 +781,10 @@ static int tune_measure(xmpi_comm* c, AnswerCheck& chk, const std::vector<TuneCa
     c->dsync_unroll = keep_unroll;
     if (tr)
       fprintf(stderr, "[xmpi %d %.6f] tune:   %s %zu B by %s: %.0f us%s; arm %.1f ms, first run %.1f ms, verdict %.1f ms, all %.1f ms\n", c->rank, now_seconds(),
-              coll_name(coll), per_rank, kCandName[k], iters > 0 ? us[k] : 0.0, check ? " (checked)" : "", t_arm * 1e3, t_run * 1e3, t_verdict * 1e3,
+              coll_name(coll), per_rank, xmpi_comm::kCandName[k], iters > 0 ? us[k] : 0.0, check ? " (checked)" : "", t_arm * 1e3, t_run * 1e3, t_verdict * 1e3,
               (now_seconds() - tb) * 1e3);
     if (rc == XMPI_ERR_TIMEOUT && keep_timeout == 0)
-      set_last_error(std::string(coll_name(coll)) + " by " + kCandName[k] + " at " + std::to_string(per_rank) + " B per rank did not complete within " +
+      set_last_error(std::string(coll_name(coll)) + " by " + xmpi_comm::kCandName[k] + " at " + std::to_string(per_rank) + " B per rank did not complete within " +
                      std::to_string(kTuneTimeoutS) + " s while the library was checking / timing it on this machine (" + xmpi_last_error() +
                      "): leave it out (xmpi_set_param \"tune_mask\") or give the job a no-progress limit (XMPI_TIMEOUT_S)");
   }
@@ -927,7 +924,7 @@ static int init_selfcheck(xmpi_comm* c) {
   auto reject = [&](int coll, int k, size_t per_rank, uint64_t nbad) {
     c->tune_rejected[coll] |= 1u << k;
     char t[200];
-    snprintf(t, sizeof t, "%s: %s gives wrong answers on this machine (%zu B per rank: %llu bytes differ on the worst rank)", coll_name(coll), kCandName[k],
+    snprintf(t, sizeof t, "%s: %s gives wrong answers on this machine (%zu B per rank: %llu bytes differ on the worst rank)", coll_name(coll), xmpi_comm::kCandName[k],
              per_rank, (unsigned long long)nbad);
     why += std::string(why.empty() ? "" : "; ") + t;
   };
@@ -2629,7 +2626,7 @@ int xmpi_tune(xmpi_comm* c, size_t max_bytes) {
           rejected |= 1u << k;
           char t[200];
           snprintf(t, sizeof t, "%s: %s gives wrong answers on this machine (first at %zu B per rank: %llu bytes differ on the worst rank)", coll_name(coll),
-                   kCandName[k], per_rank, (unsigned long long)worst_bad[k]);
+                   xmpi_comm::kCandName[k], per_rank, (unsigned long long)worst_bad[k]);
           why += std::string(why.empty() ? "" : "; ") + t;
         }
       rows.push_back({per_rank, worst});

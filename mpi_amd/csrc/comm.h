@@ -177,6 +177,10 @@ struct xmpi_comm {
   // The candidates by number: what tune_mask and tune_rejected_<collective> name bit by bit.
   enum { CAND_FOLD = 0, CAND_FOLD_U2 = 1, CAND_SPLIT = 2, CAND_ZPUSH = 3, CAND_RING = 4, CAND_RHD = 5, CAND_LL = 6, CAND_RING_PUSH = 7,
          CAND_RHD_PUSH = 8, CAND_TREE = 9, CAND_TREE_PUSH = 10, CAND_COUNT = 11 };
+  // ... and by name: what the tuner's report, the self-check's and a refusal call them
+  static constexpr const char* kCandName[CAND_COUNT] = {"fold (one kernel)", "fold (one kernel, 2 packets in flight)", "split (meet / body / done)",
+                                                        "push-only", "ring kernel", "halving kernel", "LL lines", "ring kernel, push form",
+                                                        "halving kernel, push form", "tree kernel", "tree kernel, push form"};
   // Schedules whose ANSWERS were wrong on this machine (xmpi_tune and xmpi_init's self-check run every candidate once on patterned
   // inputs whose sum is exact in any association, compare with the locally computed result and vote: wrong on ANY rank = rejected on
   // EVERY rank).  A rejected schedule is never AUTO's choice again and a caller who names it is refused -- the same on every rank.

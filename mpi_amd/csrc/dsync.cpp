@@ -532,6 +532,39 @@ void reap_deferred(xmpi_comm* c, bool wait) {
   }
 }
 
+// blocks that kernels enqueued so far may still use go back once the stream has passed them (reap_deferred) -- or, when no event
+// can be recorded behind them, at finalize (dsync_leaked): never while a kernel may still use them
+hipError_t give_back_behind(xmpi_comm* c, hipStream_t stream, std::vector<void*> bufs) {
+  if (bufs.empty()) return hipSuccess;
+  xmpi_comm::DsyncDeferred d{nullptr, std::move(bufs)};
+  hipError_t e = hipEventCreateWithFlags(&d.done, hipEventDisableTiming);
+  if (e == hipSuccess && (e = hipEventRecord(d.done, stream)) != hipSuccess) (void)hipEventDestroy(d.done);
+  if (e == hipSuccess) {
+    c->dsync_deferred.push_back(std::move(d));
+  } else {
+    (void)hipGetLastError();
+    c->dsync_leaked.insert(c->dsync_leaked.end(), d.bufs.begin(), d.bufs.end());
+  }
+  return e;
+}
+
+// a block of the registered arenas standing in for memory the peers cannot map: lent (into `lent`, whose owner gives it back) and
+// exported.  nullptr: *rc says why.  The copy in -- and what a failed one means -- is the caller's.
+void* lend_standin(xmpi_comm* c, std::vector<void*>& lent, size_t bytes, BufRef* ref, int* rc) {
+  void* p = heap_alloc(c->device, bytes);
+  if (!p) {
+    *rc = XMPI_ERR_NOMEM;
+    return nullptr;
+  }
+  lent.push_back(p);
+  if (!zc_export(c, p, bytes, ref)) {
+    *rc = XMPI_ERR_HIP;
+    return nullptr;
+  }
+  c->dsync_bounced++;
+  return p;
+}
+
 struct Resolved {
   const void* send = nullptr;
   void* recv = nullptr;
@@ -540,7 +573,12 @@ struct Resolved {
   void* tmp_recv = nullptr;
 };
 
-}  // namespace
+// a collective's arguments, as its steps read them
+struct CollArgs {
+  int coll, root, dtype, op;
+  size_t count, es;               // elements per rank, bytes per element
+  size_t send_bytes, recv_bytes;  // per rank; allgather's receive buffer holds N blocks
+};
 
 // pinned memory for the host slices of blocking collectives; false = not available (the runtime's own staged copies serve)
 static bool host_bounce_ready(xmpi_comm* c) {
@@ -639,64 +677,173 @@ static int order_behind_last(xmpi_comm* c, hipStream_t stream, bool capturing) {
   return XMPI_OK;
 }
 
+// What one collective borrows -- stand-ins lent from the registered arenas, the landing block it outgrew, the sampled events, the
+// done word -- and the three ways it gives them back: fail (nothing more runs for it), enqueued (the stream gives the blocks back
+// once it has passed the call) and wait_and_finish (a blocking call's tail).
+struct DsyncCall {
+  xmpi_comm* const c;
+  const hipStream_t stream;
+  const bool blocking;
+  // THIS call's number (what its XMPI_ENTER drew), not the counter as it stands now: another thread of the communicator may have
+  // entered since -- it waits for coll_mu, is counted already, and what it goes on to enqueue is not this call's to vouch for
+  const uint64_t calls = t_api_call;
+  std::vector<void*> lent;        // stand-ins
+  void* outgrown = nullptr;       // the landing block own_block replaced (one per call at most)
+  bool sampled = false;           // the launches carry begin / end events ...
+  hipEvent_t pstart = nullptr, pstop = nullptr;
+  size_t traffic = 0;             // ... and the profile counts this many bytes for them
+  uint64_t done_id = 0;           // the call's number in the done word ...
+  uint64_t* done_dev = nullptr;   // ... which its closing block writes when the call blocks (dsync_status bytes 16..23)
+  const void* out_src = nullptr;  // a stand-in whose contents go home to the caller's receive buffer ...
+  bool host_out = false;          // ... or: the result lies in the pinned block (host_bounce, second half)
+
+  DsyncCall(xmpi_comm* comm, hipStream_t s, bool b) : c(comm), stream(s), blocking(b) {}
+
+  void* lend(size_t bytes) {
+    void* p = heap_alloc(c->device, bytes);
+    if (p) lent.push_back(p);
+    return p;
+  }
+
+  // The communicator KEEPS one registered block for what a stepped collective needs beside the caller's buffers -- the push forms'
+  // landing block, the pull-form tree reduce's accumulator -- and uses it again for the next one (grown when one needs more): the
+  // peers touch it only between this rank's announce for a collective and its close, and its kernels run one at a time -- so
+  // back-to-back enqueued collectives share one block, where a block lent per call would have each of them take a new one before
+  // the stream has given the last one back (1 GiB fp16, halving push form, 5 enqueued steps: a new 1 GiB arena allocated,
+  // exported and mapped by every peer per step -- 100 ms instead of 9).
+  void* own_block(size_t bytes) {
+    if (!c->land_block || c->land_block_bytes < bytes) {
+      // the outgrown block goes back once THIS collective's kernel -- behind every earlier one -- has passed.  Not through `lent`:
+      // a failure gives `lent` back at once, and earlier ENQUEUED collectives may still be landing in this block
+      if (c->land_block) outgrown = c->land_block;
+      c->land_block = heap_alloc(c->device, bytes);
+      c->land_block_bytes = c->land_block ? bytes : 0;
+    }
+    return c->land_block;
+  }
+
+  // behind order_behind_last, before the first launch: the call's number, and whether its launches are sampled
+  void begin(bool capturing) {
+    done_id = ++c->dsync_done_seq;
+    done_dev = (blocking && c->dsync_status_dev) ? (uint64_t*)(c->dsync_status_dev + 4) : nullptr;
+    sampled = !capturing && c->prof_on && (c->prof_seq[PROF_ZCOPY]++ % (uint64_t)std::max<long>(1, c->prof_every)) == 0;
+  }
+
+  // sampled launches carry their own begin / end events (attached to the dispatch); a launch that is only enqueued
+  // leaves them for the next blocking call to read, so sampling does not put a host wait between enqueued steps
+  bool prof_events() {
+    if (sampled && !pstart) {
+      pstart = ev_get(c, true);
+      pstop = ev_get(c, true);
+      if (!pstart || !pstop) return false;
+    }
+    return true;
+  }
+  void keep_prof() {
+    if (pstart) c->dsync_prof_pending.push_back({pstart, pstop, traffic});
+    pstart = pstop = nullptr;
+  }
+
+  // a failure once blocks are borrowed or the epoch has advanced: the stand-ins go back at once, the outgrown block behind what
+  // the stream holds, and the peers -- whose kernels would wait for this rank -- are told through the job's abort flag
+  int fail(int rc) {
+    for (void* p : lent) (void)heap_free(p);
+    lent.clear();
+    if (outgrown) (void)give_back_behind(c, stream, {outgrown});
+    outgrown = nullptr;
+    c->ctl->set_abort(rc);
+    return rc;
+  }
+
+  // The result of a stand-in goes home, the blocks go back.  (A copy into pageable host memory blocks the calling thread until
+  // the kernel before it has ended -- and the kernel ends only when every peer has arrived, which a peer may be unable to do
+  // before THIS rank has mapped a buffer it just registered.  So a blocking call copies out after its polling wait, which serves
+  // the peers; the stream-ordered forms take device memory only, where the copy really is asynchronous.)
+  int enqueued(void* home, size_t bytes) {
+    keep_prof();
+    if (out_src) {
+      const hipError_t e = hipMemcpyAsync(home, out_src, bytes, hipMemcpyDefault, stream);
+      if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync(result of a stand-in)", __FILE__, __LINE__));
+    }
+    if (outgrown) lent.push_back(outgrown);
+    outgrown = nullptr;
+    const hipError_t e = give_back_behind(c, stream, std::move(lent));
+    lent.clear();
+    return e == hipSuccess ? XMPI_OK : fail(hip_fail(e, "hipEventRecord(blocks lent to an enqueued collective)", __FILE__, __LINE__));
+  }
+
+  int wait_and_finish(void* home, size_t bytes) {
+    const int rc = wait_blocking(c, stream, done_dev != nullptr, done_id);
+    if (rc != XMPI_OK) return fail(rc);
+    // (the kernel's last act was the word this call waited for; everything before it on the streams is over -- unless another
+    // thread has entered the library meanwhile.  The next blocking small collective need not ask the streams: dsync_ll)
+    if (c->api_calls.load(std::memory_order_relaxed) == calls) c->agent_quiet_at = calls;
+    if (outgrown) lent.push_back(outgrown);  // (the stream has passed this collective, and with it every earlier one)
+    outgrown = nullptr;
+    if (host_out) {
+      memcpy(home, c->host_bounce + xmpi_comm::kHostBounce, bytes);
+    } else if (out_src) {
+      hipError_t e = hipMemcpyAsync(home, out_src, bytes, hipMemcpyDefault, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      if (e != hipSuccess) return fail(hip_fail(e, "copy of a stand-in's result", __FILE__, __LINE__));
+    }
+    for (void* p : lent) (void)heap_free(p);
+    lent.clear();
+    keep_prof();
+    dsync_prof_harvest(c);
+    return dsync_check(c);
+  }
+};
+
+}  // namespace
+
 // ---- LL small collectives (ll.hip): the payload is pushed into the peers' flag allocations, nothing is registered,
 // announced or translated; one kernel, one one-way hop.  Whether a call goes this way is decided by dsync_collective from the
 // arguments and the job's layout only (the same on every rank); what kind of memory a rank passes is this rank's business.
-static int dsync_ll(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype, int op,
-                    hipStream_t stream, bool blocking, bool capturing) {
-  const int N = c->size, me = c->rank;
-  const size_t unit = count * xmpi_dtype_size((xmpi_dtype)dtype);
-  const size_t recv_bytes = coll == COLL_ALLGATHER ? unit * (size_t)N : unit;
+static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, void* recvbuf, bool capturing) {
+  xmpi_comm* const c = call.c;
+  const hipStream_t stream = call.stream;
+  const bool blocking = call.blocking;
+  const int N = c->size, me = c->rank, coll = k.coll, root = k.root;
+  const size_t unit = k.send_bytes, recv_bytes = k.recv_bytes;
   RoctxRange range("xmpi:dsync %s form=ll bytes=%zu epoch=%llu %s", coll_name(coll), unit, (unsigned long long)c->dsync_epoch + 1,
                    blocking ? "blocking" : "enqueued");
   const bool reads = coll != COLL_BCAST || me == root;           // this rank's send buffer is read
   const bool writes = (coll != COLL_REDUCE || me == root) && !(coll == COLL_BCAST && me == root);  // its receive buffer is written
-  std::vector<void*> lent;
-  auto fail = [&](int rc) {
-    for (void* p : lent) (void)heap_free(p);
-    c->ctl->set_abort(rc);
-    return rc;
-  };
   auto on_gpu = [&](const void* p, size_t bytes) {
     BufRef ref;
     return zc_export(c, p, bytes, &ref) || is_device_pointer(p);
   };
   const void* send = sendbuf;
   void* recv = recvbuf;
-  void* out_tmp = nullptr;   // a stand-in whose contents go home to recvbuf
-  bool host_out = false;     // ... or the result lies in the pinned block
-  if (reads && !on_gpu(sendbuf, unit)) {  // a host slice: through pinned memory the kernel reads itself, or a stand-in
-    if (capturing) {
-      set_last_error("graph capture needs device buffers");
-      return XMPI_ERR_ARG;
-    }
+  // a host slice: through pinned memory the kernel reads / writes itself, or a stand-in
+  const bool host_in = reads && !on_gpu(sendbuf, unit), host_res = writes && !on_gpu(recvbuf, recv_bytes);
+  if (capturing && (host_in || host_res)) {
+    set_last_error("graph capture needs device buffers");
+    return XMPI_ERR_ARG;
+  }
+  if (host_in) {
     if (blocking && host_bounce_ready(c)) {
       memcpy(c->host_bounce, sendbuf, unit);
       send = c->host_bounce_dev;
       c->host_bounce_calls++;
     } else {
-      void* tmp = heap_alloc(c->device, unit);
-      if (!tmp) return fail(XMPI_ERR_NOMEM);
-      lent.push_back(tmp);
+      void* tmp = call.lend(unit);
+      if (!tmp) return call.fail(XMPI_ERR_NOMEM);
       const hipError_t ce = hipMemcpyAsync(tmp, sendbuf, unit, hipMemcpyDefault, stream);
-      if (ce != hipSuccess) return fail(hip_fail(ce, "hipMemcpyAsync(stand-in)", __FILE__, __LINE__));
+      if (ce != hipSuccess) return call.fail(hip_fail(ce, "hipMemcpyAsync(stand-in)", __FILE__, __LINE__));
       send = tmp;
     }
   }
-  if (writes && !on_gpu(recvbuf, recv_bytes)) {
-    if (capturing) {
-      set_last_error("graph capture needs device buffers");
-      return XMPI_ERR_ARG;
-    }
+  if (host_res) {
     if (blocking && recv_bytes <= xmpi_comm::kHostBounce && c->dsync_status_dev && host_bounce_ready(c)) {
       recv = c->host_bounce_dev + xmpi_comm::kHostBounce;
-      host_out = true;
+      call.host_out = true;
       c->host_bounce_calls++;
     } else {
-      out_tmp = heap_alloc(c->device, recv_bytes);
-      if (!out_tmp) return fail(XMPI_ERR_NOMEM);
-      lent.push_back(out_tmp);
-      recv = out_tmp;
+      recv = call.lend(recv_bytes);
+      if (!recv) return call.fail(XMPI_ERR_NOMEM);
+      call.out_src = recv;
     }
   }
   if (!writes) recv = const_cast<void*>(send);  // (never written; the launcher wants a pointer)
@@ -711,16 +858,14 @@ static int dsync_ll(xmpi_comm* c, int coll, int root, const void* sendbuf, void*
   // on the stream first.
   // (the streams are not asked when the previous call into the library on this communicator was itself a collective the agent
   // ran: it found them idle, and nothing has been enqueued through the library since)
-  // THIS call's number (what its XMPI_ENTER drew), not the counter as it stands now: another thread of the communicator may have
-  // entered since -- it waits for coll_mu, is counted already, and what it goes on to enqueue is not this call's to vouch for
-  const uint64_t calls = t_api_call;
+  const uint64_t calls = call.calls;
   auto idle = [](hipStream_t s) { return hipStreamQuery(s) == hipSuccess; };
   const bool quiet = calls == c->agent_quiet_at + 1, consecutive = calls == c->agent_epoch_at + 1;
   // up to agent_ll_bytes (8 KiB: a lane's two rounds of lines are waited for together -- blocking 8.8 us against 11.7 launched,
   // 2 processes; host slices 10.0 against 13.8; at 16 KiB it is a tie, 12.1 / 11.7, and beyond the launched kernel's many blocks
   // win) -- scripts/r04_agent_limit.sh
   const size_t agent_limit = (size_t)std::max<long>(0, c->agent_ll_bytes);
-  if (blocking && !capturing && lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
+  if (blocking && !capturing && call.lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
       (quiet ||
        (idle(stream) && (!c->dsync_last_stream || c->dsync_last_stream == stream || idle(c->dsync_last_stream))))) {
     ++c->dsync_epoch;
@@ -730,10 +875,10 @@ static int dsync_ll(xmpi_comm* c, int coll, int root, const void* sendbuf, void*
     // the previous one less than a patience ago -- and launching the ordinary kernel otherwise: 25.4 / 25.3 us per call, against
     // 14.4 / 21.5 with the agent started by every call (a launch into a GPU that has been idle for 100 us costs more than one into a
     // busy GPU; the agent's launch overlaps with the command already lying in its record) and 7.5 inside its patience.
-    const int took = agent_submit_ll(c, send, recv, unit, ll_coll, root, dtype, op, consecutive);
+    const int took = agent_submit_ll(c, send, recv, unit, ll_coll, root, k.dtype, k.op, consecutive);
     if (took < 0) {  // taken and never answered: the collective has failed, nothing may run for this epoch beside the agent
       set_last_error("collective: the LL agent did not answer within XMPI_TIMEOUT_S (a peer that never arrived?)");
-      return fail(XMPI_ERR_TIMEOUT);
+      return call.fail(XMPI_ERR_TIMEOUT);
     }
     if (took > 0) {
       c->agent_ll_wait_ns += (uint64_t)((now_seconds() - t_cmd) * 1e9);
@@ -742,14 +887,15 @@ static int dsync_ll(xmpi_comm* c, int coll, int root, const void* sendbuf, void*
       if (c->api_calls.load(std::memory_order_relaxed) == calls) c->agent_quiet_at = c->agent_epoch_at = calls;
       c->dsync_ll_launches++;  // (an LL collective, whoever ran its lines)
       c->dsync_ll_agent++;
-      if (host_out) memcpy(recvbuf, c->host_bounce + xmpi_comm::kHostBounce, recv_bytes);
+      if (call.host_out) memcpy(recvbuf, c->host_bounce + xmpi_comm::kHostBounce, recv_bytes);
       return dsync_check(c);
     }
     --c->dsync_epoch;
   }
   (void)hipGetLastError();
-  int rc = order_behind_last(c, stream, capturing);
-  if (rc != XMPI_OK) return fail(rc);
+  const int rc = order_behind_last(c, stream, capturing);
+  if (rc != XMPI_OK) return call.fail(rc);
+  call.begin(capturing);
 
   DsyncLLArgs a;
   memset(&a, 0, sizeof a);
@@ -760,70 +906,29 @@ static int dsync_ll(xmpi_comm* c, int coll, int root, const void* sendbuf, void*
   a.root = root;
   a.epoch_floor = c->dsync_base;
   a.host_epoch = c->dsync_status_dev ? (uint64_t*)(c->dsync_status_dev + 2) : nullptr;
-  const uint64_t done_id = ++c->dsync_done_seq;
-  uint64_t* const done_dev = (blocking && c->dsync_status_dev) ? (uint64_t*)(c->dsync_status_dev + 4) : nullptr;
-  a.host_done = done_dev;
-  a.done_value = done_id;
+  a.host_done = call.done_dev;
+  a.done_value = call.done_id;
   a.send = send;
   a.recv = recv;
   a.bytes = unit;
   a.abort_word = c->dsync_abort_dev;
   a.status = c->dsync_status_dev;
   a.spin_limit = c->timeout_s > 0 ? (uint64_t)c->timeout_s * 100000000ull : 0;
-  hipEvent_t pstart = nullptr, pstop = nullptr;
-  const bool sampled = !capturing && c->prof_on && (c->prof_seq[PROF_ZCOPY]++ % (uint64_t)std::max<long>(1, c->prof_every)) == 0;
-  if (sampled) {
-    pstart = ev_get(c, true);
-    pstop = ev_get(c, true);
-    if (!pstart || !pstop) return fail(XMPI_ERR_HIP);
-  }
+  if (!call.prof_events()) return call.fail(XMPI_ERR_HIP);
   ++c->dsync_epoch;
   {
-    const hipError_t le = launch_dsync_ll(a, dtype, op, stream, pstart, pstop);
+    const hipError_t le = launch_dsync_ll(a, k.dtype, k.op, stream, call.pstart, call.pstop);
     if (le != hipSuccess) {  // nothing was enqueued: the host's count goes back, the lent blocks too, and the peers -- whose kernels
       --c->dsync_epoch;      // wait for this rank's lines -- are told through the job's abort flag (fail)
-      return fail(hip_fail(le, "LL kernel launch", __FILE__, __LINE__));
+      return call.fail(hip_fail(le, "LL kernel launch", __FILE__, __LINE__));
     }
   }
   c->dsync_launches++;
   c->dsync_ll_launches++;
   if (!capturing) c->dsync_last_stream = stream;
-  const size_t traffic = 2 * unit * (size_t)N;  // (own payload read, N-1 pushes of twice its size ... : a latency path, not a bandwidth one)
-  if (pstart) c->dsync_prof_pending.push_back({pstart, pstop, traffic});
-  if (!blocking) {
-    if (out_tmp) {
-      const hipError_t ce = hipMemcpyAsync(recvbuf, out_tmp, recv_bytes, hipMemcpyDefault, stream);
-      if (ce != hipSuccess) return fail(hip_fail(ce, "hipMemcpyAsync(result of a stand-in)", __FILE__, __LINE__));
-    }
-    if (!lent.empty()) {
-      xmpi_comm::DsyncDeferred d;
-      if (hipEventCreateWithFlags(&d.done, hipEventDisableTiming) != hipSuccess) return fail(XMPI_ERR_HIP);
-      const hipError_t re = hipEventRecord(d.done, stream);
-      if (re != hipSuccess) {
-        (void)hipEventDestroy(d.done);
-        return fail(hip_fail(re, "hipEventRecord", __FILE__, __LINE__));
-      }
-      d.bufs = lent;
-      c->dsync_deferred.push_back(d);
-    }
-    return XMPI_OK;
-  }
-  rc = wait_blocking(c, stream, done_dev != nullptr, done_id);
-  if (rc != XMPI_OK) return fail(rc);
-  // (the kernel's last act was the word this call waited for; everything before it on the streams is over -- unless another thread
-  // has entered the library meanwhile)
-  if (c->api_calls.load(std::memory_order_relaxed) == calls) c->agent_quiet_at = calls;
-  if (host_out) {
-    memcpy(recvbuf, c->host_bounce + xmpi_comm::kHostBounce, recv_bytes);
-  } else if (out_tmp) {
-    hipError_t ce = hipMemcpyAsync(recvbuf, out_tmp, recv_bytes, hipMemcpyDefault, stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(stream);
-    if (ce != hipSuccess) return fail(hip_fail(ce, "copy of a stand-in's result", __FILE__, __LINE__));
-  }
-  for (void* p : lent) (void)heap_free(p);
-  lent.clear();
-  dsync_prof_harvest(c);
-  return dsync_check(c);
+  call.traffic = 2 * unit * (size_t)N;  // (own payload read, N-1 pushes of twice its size ... : a latency path, not a bandwidth one)
+  call.keep_prof();
+  return blocking ? call.wait_and_finish(recvbuf, recv_bytes) : call.enqueued(recvbuf, recv_bytes);
 }
 
 bool dsync_usable(const xmpi_comm* c) { return c->dsync_ok && c->dsync && c->size > 1; }
@@ -884,55 +989,32 @@ void dsync_graph_launched(xmpi_comm* c, hipStream_t stream, bool before) {
   (void)hipGetLastError();
 }
 
-// the library's schedule for an AUTO call (xmpi_tune fills the table; untuned: the zero-copy fold, split by size)
-static void tuned_choice(const xmpi_comm* c, int coll, size_t bytes, int* algo, int* split, int* unroll) {
-  int k = 0;
-  while (k + 1 < xmpi_comm::kTuneClasses && (bytes >> (k + 9)) != 0) k++;
-  if (c->tuned && coll >= 0 && coll < 4) {
-    if (c->tune_algo[coll][k] >= 0) *algo = c->tune_algo[coll][k];
-    if (c->tune_split[coll][k] >= 0) *split = c->tune_split[coll][k];
-    if (c->tune_unroll[coll][k] > 0) *unroll = c->tune_unroll[coll][k];
-  }
-}
+namespace {
 
-// the call signature the kernels announce and compare (DsyncArgs::sig)
-static inline uint64_t sig_mix(uint64_t h, uint64_t v) {
-  h = (h ^ v) * 0x100000001B3ull;
-  return h ^ (h >> 29);
-}
-static inline uint64_t sig_fold(uint64_t h) { return std::max<uint64_t>(1, (h ^ (h >> 32)) & 0xffffffffull); }
+struct DsyncRoute {
+  enum Form { LL, FOLD, PUSH_ONLY, STEPPED } form = FOLD;  // FOLD: one kernel or meet / body / done (bcast and allgather: theirs)
+  int algo = XMPI_ALGO_AUTO;        // the schedule as it runs: after the table and the capture demotions
+  int sched_algo = XMPI_ALGO_AUTO;  // ... a stepped kernel by its pull form's name (RING, RHD, TREE)
+  bool sched_push = false;          // ... and whether it pushes
+  int split_pref = -1;              // one kernel (0) or meet / body / done (1); -1: by size (dsync_split_bytes)
+  int unroll = 1;
+  int refused = -1;                 // the rejected candidate (xmpi_comm::CAND_*) the caller named: nothing runs; -1: none
+};
 
-// a HIP failure inside a collective that has already borrowed blocks or advanced the epoch: the blocks go back and the peers --
-// whose kernels would wait for this rank -- are told through the job's abort flag (the function's `fail`)
-#define DS_HIP(call)                                                                 \
-  do {                                                                               \
-    const hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return fail(::xmpi::hip_fail(_e, #call, __FILE__, __LINE__)); \
-  } while (0)
-
-// One device-synchronised collective, enqueued on `stream`.  blocking: wait for it (the xmpi_allreduce family);
-// otherwise return once it is enqueued (xmpi_*_on_stream).  Every rank of the job takes this path for the same
-// calls (the decision depends on the communicator and the arguments only), so the epochs agree.
-int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,
-                     int op, hipStream_t stream, bool blocking, int algo) {
-  const int N = c->size, me = c->rank;
-  const size_t es = xmpi_dtype_size((xmpi_dtype)dtype);
-  const size_t send_bytes = count * es;
-  const size_t recv_bytes = (coll == COLL_ALLGATHER) ? send_bytes * (size_t)N : send_bytes;
-  const bool recv_significant = (coll != COLL_REDUCE) || me == root;
-  if (!stream) stream = c->local_stream;
-  const uint64_t calls_at_entry = t_api_call;  // (dsync_ll's shortcut: see agent_quiet_at)
-  dsync_service(c);
-  reap_deferred(c, false);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
-  (void)hipGetLastError();
-  const bool capturing = cap != hipStreamCaptureStatusNone;
-
-  // the schedule: what the caller named, or the library's own table
-  int split_pref = -1, unroll = (int)std::max<long>(1, std::min<long>(2, c->dsync_unroll));
+// From the communicator and the arguments only -- the same answer on every rank, so every rank refuses alike, hands the same calls
+// to LL and launches the same form.  Pure: no HIP, no counters, no error text.
+DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t send_bytes, bool capturing) {
+  DsyncRoute rt;
+  rt.unroll = (int)std::max<long>(1, std::min<long>(2, c->dsync_unroll));
+  // the schedule: what the caller named, or the library's own table (xmpi_tune fills it; untuned: the zero-copy fold, split by size)
   if (algo == XMPI_ALGO_AUTO) {
-    tuned_choice(c, coll, send_bytes, &algo, &split_pref, &unroll);
+    int cls = 0;
+    while (cls + 1 < xmpi_comm::kTuneClasses && (send_bytes >> (cls + 9)) != 0) cls++;
+    if (c->tuned && coll >= 0 && coll < 4) {
+      if (c->tune_algo[coll][cls] >= 0) algo = c->tune_algo[coll][cls];
+      if (c->tune_split[coll][cls] >= 0) rt.split_pref = c->tune_split[coll][cls];
+      if (c->tune_unroll[coll][cls] > 0) rt.unroll = c->tune_unroll[coll][cls];
+    }
     // untuned: short messages go as {data, flag} lines (ll.hip) -- one one-way hop instead of two round trips
     if (algo == XMPI_ALGO_AUTO && c->zero_copy && send_bytes <= (size_t)std::max<long>(0, c->ll_bytes)) algo = XMPI_ALGO_LL;
   }
@@ -941,179 +1023,434 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   // rules), so this is a caller -- or a table written by hand -- naming it.  Every rank refuses alike, before anything is lent,
   // announced or moved.
   const uint32_t rejected = (c->tune_running || coll < 0 || coll >= 4) ? 0u : c->tune_rejected[coll];
-  auto refuse = [&](int cand) {
-    static const char* const what[] = {"the one-kernel fold", "the one-kernel fold", "meet / body / done", "push-only", "the ring kernel", "the halving kernel",
-                                       "LL lines", "the ring kernel's push form", "the halving kernel's push form", "the tree kernel", "the tree kernel's push form"};
-    set_last_error(std::string(coll_name(coll)) + " by " + what[cand] + ": refused -- it gave wrong answers on this machine when the library checked it (xmpi_get_param "
-                   "\"tune_rejected_" + std::to_string(coll) + "\"; xmpi_degraded() says where)");
-    return XMPI_ERR_UNSUPPORTED;
-  };
+  auto no = [rejected](int cand) { return ((rejected >> cand) & 1u) != 0; };
   if (algo == XMPI_ALGO_LL) {
     if (send_bytes <= kLLMaxPayload) {
-      if ((rejected >> xmpi_comm::CAND_LL) & 1u) return refuse(xmpi_comm::CAND_LL);
-      return dsync_ll(c, coll, root, sendbuf, recvbuf, count, dtype, op, stream, blocking, capturing);
+      rt.form = DsyncRoute::LL;
+      rt.algo = algo;
+      if (no(xmpi_comm::CAND_LL)) rt.refused = xmpi_comm::CAND_LL;
+      return rt;
     }
     algo = XMPI_ALGO_ZCOPY;  // named, but too long for the slots: the fold (the same decision on every rank)
   }
   // the push forms of the stepped kernels: the same schedule, the data stored into the peer instead of loaded from it
-  bool sched_push = algo == XMPI_ALGO_RING_PUSH || algo == XMPI_ALGO_RHD_PUSH || algo == XMPI_ALGO_TREE_PUSH;
-  int sched_algo = algo == XMPI_ALGO_RING_PUSH ? XMPI_ALGO_RING : algo == XMPI_ALGO_RHD_PUSH ? XMPI_ALGO_RHD
-                   : algo == XMPI_ALGO_TREE_PUSH ? XMPI_ALGO_TREE : algo;
+  rt.sched_push = algo == XMPI_ALGO_RING_PUSH || algo == XMPI_ALGO_RHD_PUSH || algo == XMPI_ALGO_TREE_PUSH;
+  rt.sched_algo = algo == XMPI_ALGO_RING_PUSH ? XMPI_ALGO_RING : algo == XMPI_ALGO_RHD_PUSH ? XMPI_ALGO_RHD
+                  : algo == XMPI_ALGO_TREE_PUSH ? XMPI_ALGO_TREE : algo;
   if (capturing) {
     // A graph cannot hold what is lent per call -- a landing block, the tree reduce's accumulator: replays would use it after it
     // went back to the arena.  Captured, a push form runs as its pull form (the same operands, order and association: the same
     // bits) and the tree reduce as the fold -- whatever named them, the caller or the tuner's table.  Every rank captures a
     // collective or none does (as with push-only below), so every rank decides alike: by the arguments, not by what IT would lend.
-    if (sched_push) algo = sched_algo;
-    sched_push = false;
-    if (sched_algo == XMPI_ALGO_TREE && coll == COLL_REDUCE) algo = sched_algo = XMPI_ALGO_ZCOPY;
+    if (rt.sched_push) algo = rt.sched_algo;
+    rt.sched_push = false;
+    if (rt.sched_algo == XMPI_ALGO_TREE && coll == COLL_REDUCE) algo = rt.sched_algo = XMPI_ALGO_ZCOPY;
   }
-  const bool stepped = (sched_algo == XMPI_ALGO_RING && (coll == COLL_ALLREDUCE || coll == COLL_ALLGATHER)) ||
-                       (sched_algo == XMPI_ALGO_RHD && coll == COLL_ALLREDUCE) ||
-                       (sched_algo == XMPI_ALGO_TREE && (coll == COLL_BCAST || coll == COLL_REDUCE));
-  const bool push = algo == XMPI_ALGO_ZPUSH;
-  if (rejected) {
-    const bool fold_no = (rejected >> xmpi_comm::CAND_FOLD) & 1u, split_no = (rejected >> xmpi_comm::CAND_SPLIT) & 1u;
-    if (stepped) {
-      const int cand = sched_algo == XMPI_ALGO_RING ? (sched_push ? xmpi_comm::CAND_RING_PUSH : xmpi_comm::CAND_RING)
-                       : sched_algo == XMPI_ALGO_RHD ? (sched_push ? xmpi_comm::CAND_RHD_PUSH : xmpi_comm::CAND_RHD)
-                                                     : (sched_push ? xmpi_comm::CAND_TREE_PUSH : xmpi_comm::CAND_TREE);
-      if ((rejected >> cand) & 1u) return refuse(cand);
-    } else if (push && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE) && !capturing) {
-      if ((rejected >> xmpi_comm::CAND_ZPUSH) & 1u) return refuse(xmpi_comm::CAND_ZPUSH);
-    } else if (coll == COLL_BCAST) {  // (its fold is one kernel whatever the size)
-      if (fold_no) return refuse(xmpi_comm::CAND_FOLD);
-    } else {
-      // one kernel or meet / body / done is each rank's own choice (the two mix: dsync_begin / the meet kernel speak one protocol):
-      // a rank keeps to the one of the two that is right here
-      if (fold_no && split_no) return refuse(xmpi_comm::CAND_FOLD);
-      if (split_no) split_pref = 0;
-      else if (fold_no && c->dsync_res) split_pref = 1;
-    }
+  rt.algo = algo;
+  const int s = rt.sched_algo;
+  if ((s == XMPI_ALGO_RING && (coll == COLL_ALLREDUCE || coll == COLL_ALLGATHER)) || (s == XMPI_ALGO_RHD && coll == COLL_ALLREDUCE) ||
+      (s == XMPI_ALGO_TREE && (coll == COLL_BCAST || coll == COLL_REDUCE))) {
+    rt.form = DsyncRoute::STEPPED;
+    const int cand = s == XMPI_ALGO_RING ? (rt.sched_push ? xmpi_comm::CAND_RING_PUSH : xmpi_comm::CAND_RING)
+                     : s == XMPI_ALGO_RHD ? (rt.sched_push ? xmpi_comm::CAND_RHD_PUSH : xmpi_comm::CAND_RHD)
+                                          : (rt.sched_push ? xmpi_comm::CAND_TREE_PUSH : xmpi_comm::CAND_TREE);
+    if (no(cand)) rt.refused = cand;
+  } else if (algo == XMPI_ALGO_ZPUSH && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE) && !capturing) {
+    // (under capture the push-only form is the fold: its staging area is a block the communicator may replace later)
+    rt.form = DsyncRoute::PUSH_ONLY;
+    if (no(xmpi_comm::CAND_ZPUSH)) rt.refused = xmpi_comm::CAND_ZPUSH;
+  } else if (coll == COLL_BCAST) {  // (its fold is one kernel whatever the size)
+    if (no(xmpi_comm::CAND_FOLD)) rt.refused = xmpi_comm::CAND_FOLD;
+  } else {
+    // one kernel or meet / body / done is each rank's own choice (the two mix: dsync_begin / the meet kernel speak one protocol):
+    // a rank keeps to the one of the two that is right here
+    if (no(xmpi_comm::CAND_FOLD) && no(xmpi_comm::CAND_SPLIT)) rt.refused = xmpi_comm::CAND_FOLD;
+    else if (no(xmpi_comm::CAND_SPLIT)) rt.split_pref = 0;
+    else if (no(xmpi_comm::CAND_FOLD) && c->dsync_res) rt.split_pref = 1;
   }
-  RoctxRange range("xmpi:dsync %s algo=%s bytes=%zu epoch=%llu %s", coll_name(coll), algo_name(algo), send_bytes,
-                   (unsigned long long)c->dsync_epoch + 1, blocking ? "blocking" : capturing ? "captured" : "enqueued");
+  return rt;
+}
 
-  // 1. buffers the peers can map.  Anything else -- host memory, device memory that was never registered --
-  //    is stood in for by a block of a registered arena (one local copy in, one out); the collective itself is
-  //    the same zero-copy exchange.
-  Resolved r;
-  r.send = sendbuf;
-  r.recv = recv_significant ? recvbuf : const_cast<void*>(sendbuf);
-  const bool in_place = sendbuf == recvbuf;
-  std::vector<void*> lent, outgrown;
-  // what may still be in use by collectives enqueued EARLIER goes back behind an event on the stream (or, failing that, at finalize)
-  auto defer_free = [&](std::vector<void*>& bufs) {
-    if (bufs.empty()) return;
-    xmpi_comm::DsyncDeferred d;
-    if (hipEventCreateWithFlags(&d.done, hipEventDisableTiming) == hipSuccess && hipEventRecord(d.done, stream) == hipSuccess) {
-      d.bufs = bufs;
-      c->dsync_deferred.push_back(d);
-    } else {
-      (void)hipGetLastError();
-      for (void* p : bufs) c->dsync_leaked.push_back(p);  // given back by dsync_finalize
+int refuse(int coll, int cand) {
+  set_last_error(std::string(coll_name(coll)) + " by " + xmpi_comm::kCandName[cand] + ": refused -- it gave wrong answers on this machine when "
+                 "the library checked it (xmpi_get_param \"tune_rejected_" + std::to_string(coll) + "\"; xmpi_degraded() says where)");
+  return XMPI_ERR_UNSUPPORTED;
+}
+
+// the call signature the kernels announce and compare (DsyncArgs::sig)
+inline uint64_t sig_mix(uint64_t h, uint64_t v) {
+  h = (h ^ v) * 0x100000001B3ull;
+  return h ^ (h >> 29);
+}
+inline uint64_t sig_fold(uint64_t h) { return std::max<uint64_t>(1, (h ^ (h >> 32)) & 0xffffffffull); }
+
+// bcast: the root stores into every buffer itself -- two ranks, or up to zc_bcast_push_bytes -- or scatters, and every rank forwards
+bool bcast_forwards(const xmpi_comm* c, size_t bytes) { return c->size > 2 && bytes > (size_t)std::max<long>(0, c->zc_bcast_push_bytes); }
+
+// What this call is, for the peers to compare with theirs (kdev.h dsync_begin): ranks that are not in the same collective, on the
+// same schedule, over the same bytes end with an error before any of them has touched another's memory -- instead of a hang, or
+// of a fold over buffers of different lengths.  (One kernel or meet / body / done is NOT part of it: those mix.)
+uint64_t call_sig(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt) {
+  const bool reduces = k.coll == COLL_ALLREDUCE || k.coll == COLL_REDUCE, rooted = k.coll == COLL_BCAST || k.coll == COLL_REDUCE;
+  const uint64_t form = rt.form == DsyncRoute::STEPPED ? 16u + 2u * (uint64_t)rt.sched_algo + (rt.sched_push ? 1u : 0u)
+                        : rt.form == DsyncRoute::PUSH_ONLY ? 2u
+                        : (k.coll == COLL_BCAST && bcast_forwards(c, k.send_bytes)) ? 3u : 1u;
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+  for (uint64_t v : {(uint64_t)k.coll + 1, form, (uint64_t)k.send_bytes, reduces ? (uint64_t)k.dtype + 1 : 0, reduces ? (uint64_t)k.op + 1 : 0,
+                     rooted ? (uint64_t)k.root + 1 : 0})
+    h = sig_mix(h, v);
+  return sig_fold(h);
+}
+
+// one kernel of the fold family (launch_fold: one kernel, or meet / body / done): its segments, the sources each folds (1: a copy,
+// in bytes) and the bytes it moves
+struct FoldStep {
+  int32_t nseg = 0;
+  DsyncSeg seg[kDsyncRanks] = {};
+  int nsrc = 1, dtype = XMPI_U8, op = XMPI_SUM;
+  size_t packets = 0, moved = 0;
+  int split_pref = 0;
+};
+// ... a form is one or two of them, the second behind the first's close; land: the block its peers store into (0: none)
+struct FoldPlan {
+  FoldStep k[2];
+  int kernels = 1;
+  size_t land = 0;
+};
+
+uint32_t everyone(int n) { return n >= 32 ? 0xffffffffu : ((1u << n) - 1u); }
+
+// allreduce / reduce: every rank folds its chunk of everybody's send buffer, in rank order, into everybody's receive buffer (reduce:
+// the root's)
+FoldPlan plan_fold(const xmpi_comm* c, const CollArgs& k, int split_pref) {
+  const int N = c->size;
+  size_t off = 0, cnt = 0;
+  zc_chunk(k.count, k.es, N, c->rank, &off, &cnt);
+  FoldPlan p;
+  FoldStep& s = p.k[0];
+  s.nseg = cnt > 0 ? 1 : 0;
+  s.seg[0].src_off = s.seg[0].dst_off = off * k.es;
+  s.seg[0].count = cnt;
+  s.seg[0].src_mask = everyone(N);
+  s.seg[0].dst_mask = k.coll == COLL_REDUCE ? (1u << k.root) : everyone(N);
+  s.nsrc = N;
+  s.dtype = k.dtype;
+  s.op = k.op;
+  s.packets = cnt / std::max<size_t>(1, 16 / k.es);
+  s.moved = (size_t)(N + (k.coll == COLL_REDUCE ? 1 : N)) * cnt * k.es;
+  s.split_pref = split_pref;
+  return p;
+}
+
+// allgather: every rank stores its block into its place in everybody's receive buffer
+FoldPlan plan_allgather(const xmpi_comm* c, const CollArgs& k, int split_pref) {
+  FoldPlan p;
+  FoldStep& s = p.k[0];
+  s.nseg = 1;
+  s.seg[0].dst_off = (size_t)c->rank * k.send_bytes;
+  s.seg[0].count = k.send_bytes;
+  s.seg[0].src_mask = 1u << c->rank;
+  s.seg[0].dst_mask = everyone(c->size);
+  s.packets = k.send_bytes / 16;
+  s.moved = (size_t)(1 + c->size) * k.send_bytes;
+  s.split_pref = split_pref;
+  return p;
+}
+
+// bcast (`send` and `recv` are the same buffer on every rank), the root pushes: it stores into every buffer, the others only take
+// part in the rendezvous.  (The ranks differ in what they launch: the one-kernel form, whose shape does not matter.)
+FoldPlan plan_bcast_push(const xmpi_comm* c, const CollArgs& k) {
+  FoldPlan p;
+  FoldStep& s = p.k[0];
+  s.nseg = c->rank == k.root ? 1 : 0;
+  s.seg[0].count = k.send_bytes;
+  s.seg[0].src_mask = 1u << k.root;
+  s.seg[0].dst_mask = everyone(c->size) & ~(1u << k.root);
+  s.packets = k.send_bytes / 16;
+  s.moved = c->rank == k.root ? (size_t)c->size * k.send_bytes : 0;
+  return p;
+}
+
+// bcast, scatter + forward: the root scatters chunk j to rank j (one segment per destination, each over its own link), then every
+// rank forwards its chunk to the others: each link carries S/N twice instead of the root's links carrying S
+FoldPlan plan_bcast_forward(const xmpi_comm* c, const CollArgs& k) {
+  const int N = c->size, me = c->rank;
+  FoldPlan p;
+  p.kernels = 2;
+  FoldStep& s = p.k[0];
+  if (me == k.root) {
+    for (int j = 0; j < N; j++) {
+      size_t off = 0, cnt = 0;
+      zc_chunk(k.count, k.es, N, j, &off, &cnt);
+      if (j == k.root || cnt == 0) continue;
+      DsyncSeg& g = s.seg[s.nseg++];
+      g.src_off = g.dst_off = off * k.es;
+      g.count = cnt * k.es;
+      g.src_mask = 1u << k.root;
+      g.dst_mask = 1u << j;
+      s.packets = std::max(s.packets, cnt * k.es / 16);
+      s.moved += 2 * cnt * k.es;
     }
-    bufs.clear();
-  };
-  auto fail = [&](int rc) {
-    for (void* p : lent) (void)heap_free(p);
-    defer_free(outgrown);
-    c->ctl->set_abort(rc);
-    return rc;
-  };
+  }
+  size_t off = 0, cnt = 0;
+  zc_chunk(k.count, k.es, N, me, &off, &cnt);
+  FoldStep& f = p.k[1];
+  f.nseg = cnt > 0 ? 1 : 0;
+  f.seg[0].src_off = f.seg[0].dst_off = off * k.es;
+  f.seg[0].count = cnt * k.es;
+  f.seg[0].src_mask = 1u << me;
+  f.seg[0].dst_mask = everyone(N) & ~(1u << me) & ~(1u << k.root);
+  f.packets = cnt * k.es / 16;
+  f.moved = (size_t)(N - 1) * cnt * k.es;
+  return p;
+}
+
+// Push-only (XMPI_ALGO_ZPUSH): the fold with nothing READ over xGMI -- loads over a link are round trips, stores are posted.
+// Two device-synchronised kernels: every rank stores its contribution to chunk q into region `me` of rank q's own block
+// (DsyncCall::own_block: the communicator's staging area, announced with the buffers; chunks cut as the fold cuts them, zc_chunk
+// -- so in place and ragged counts work like anything else); then, all of chunk `me` being local, folds it in rank order and
+// stores the result into its place in everybody's receive buffer.  One hop each way, S / N per link direction and kernel.
+FoldPlan plan_push_only(const xmpi_comm* c, const CollArgs& k) {
+  const int N = c->size, me = c->rank;
+  size_t maxc = 0;
+  for (int q = 0; q < N; q++) {
+    size_t off = 0, cnt = 0;
+    zc_chunk(k.count, k.es, N, q, &off, &cnt);
+    maxc = std::max(maxc, cnt * k.es);
+  }
+  const size_t region = (maxc + 255) / 256 * 256;
+  FoldPlan p;
+  p.kernels = 2;
+  p.land = region * (size_t)N;
+  FoldStep& s = p.k[0];
+  for (int q = 0; q < N; q++) {
+    size_t off = 0, cnt = 0;
+    zc_chunk(k.count, k.es, N, q, &off, &cnt);
+    if (q == me || cnt == 0) continue;
+    DsyncSeg& g = s.seg[s.nseg++];
+    g.src_off = off * k.es;           // my contribution to chunk q ...
+    g.dst_off = (size_t)me * region;  // ... into region `me` of rank q's block
+    g.count = cnt * k.es;
+    g.src_mask = 1u << me;
+    g.dst_mask = 1u << q;
+    g.dst_to_land = 1;
+    s.packets = std::max(s.packets, cnt * k.es / 16);
+    s.moved += 2 * cnt * k.es;
+  }
+  // every contribution to chunk `me` is local now (the first kernel's close: every peer's stores have landed): ONE more kernel
+  // folds them in rank order and stores the result into its place in everybody's receive buffer -- the fold's own kernels
+  // (one kernel, or meet / body / done by size) with local sources.  Its rendezvous doubles as "my buffers may be written";
+  // nobody's block is written again before its owner's next collective has announced it.
+  p.k[1] = plan_fold(c, k, -1).k[0];
+  p.k[1].seg[0].src_from_recv = 2;
+  p.k[1].seg[0].stage_stride = region;
+  return p;
+}
+
+// ring / recursive halving + doubling / binary tree: ONE kernel per rank runs every step of the schedule, the steps released by
+// flag words between the peers' kernels (sched.hip) -- the schedules north_star names, without a host between their steps.
+// The kernel's arguments and shape (channels, *gx workers per channel, pieces, orders: part of the signature); returns the
+// traffic figure.
+size_t plan_sched(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt, const DsyncArgs& a, DsyncSchedArgs* out, int* gx_out) {
+  const int N = c->size, me = c->rank, coll = k.coll;
+  const size_t send_bytes = k.send_bytes;
+  const bool push = rt.sched_push;
+  DsyncSchedArgs& sa = *out;
+  memset(&sa, 0, sizeof sa);
+  sa.d = a;
+  sa.root = k.root;
+  sa.count = k.count;
+  sa.elem_size = (uint32_t)k.es;
+  sa.pieces = 1;
+  sa.push = push ? 1u : 0u;
+  size_t step_bytes = send_bytes, traffic = 0;  // what the largest step of the schedule moves
+  int nchan = 1;
+  if (rt.sched_algo == XMPI_ALGO_RING) {
+    sa.sched = coll == COLL_ALLREDUCE ? SCHED_RING_ALLREDUCE : SCHED_RING_ALLGATHER;
+    step_bytes = coll == COLL_ALLREDUCE ? (send_bytes + (size_t)N - 1) / (size_t)N : send_bytes;
+    // every channel is a different cyclic order of the ranks (plan.cpp ring_order: on an even mesh N-2 directed rings
+    // that share no link direction); ranks sharing a GPU have no links to spread over
+    const int avail = std::min(ring_channel_count(N), kMaxSchedChannels);
+    // (the shape of a stepped kernel -- channels, workers -- is protocol: worker w waits for worker w of its peer.  It follows
+    // the job's most crowded GPU, which every rank reads alike, not this rank's own: 5 ranks on 2 GPUs sit 3 + 2)
+    nchan = c->sched_channels > 0 ? (int)std::min<long>(c->sched_channels, avail) : (c->dsync_sharers_job > 1 ? 1 : avail);
+    // (reduce-scatter 2 reads + 1 write per step, allgather 1 + 1; the push form reads its own first chunk once more)
+    traffic = coll == COLL_ALLREDUCE ? (5 * (size_t)(N - 1) + (push ? 1 : 0)) * step_bytes : 2 * (size_t)N * send_bytes;
+  } else if (rt.sched_algo == XMPI_ALGO_RHD) {
+    sa.sched = SCHED_RHD_ALLREDUCE;
+    step_bytes = send_bytes / 2;
+    // halving: 3 x (S/2 + S/4 + ...), doubling: 2 x the same; push form: the landing regions are written and read -- one more
+    traffic = (push ? 6 : 5) * (send_bytes - send_bytes / (size_t)N);
+    if ((N & (N - 1)) != 0) traffic += 3 * send_bytes;     // (no power of two: the fold-in / fold-out steps, at most)
+  } else {
+    sa.sched = coll == COLL_BCAST ? SCHED_TREE_BCAST : SCHED_TREE_REDUCE;
+    const size_t piece = (size_t)std::max<long>(4096, c->tree_piece_bytes);
+    sa.pieces = (int)std::min<size_t>(32, std::max<size_t>(1, (send_bytes + piece - 1) / piece));
+    step_bytes = (send_bytes + (size_t)sa.pieces - 1) / (size_t)sa.pieces;
+    const int v = (me - k.root + N) % N;
+    const size_t children = (size_t)((2 * v + 1 < N) + (2 * v + 2 < N));
+    if (coll == COLL_BCAST) {  // pull: a node reads its parent's piece and writes its own; push: it reads its own and writes each child's
+      traffic = push ? 2 * send_bytes * children : (me == k.root ? 0 : 2 * send_bytes);
+    } else {  // pull: 2 reads + 1 write per child; push: own input + one slot per child read, one buffer stored (upwards, or the result)
+      traffic = push ? (children + 2) * send_bytes : 3 * send_bytes * children;
+    }
+  }
+  const size_t tiles = std::max<size_t>(1, (step_bytes + kSchedTileBytes - 1) / kSchedTileBytes);
+  const long job_cap = c->dsync_grid_cap > 0 ? c->dsync_grid_cap : 1024 / std::max(1, c->dsync_sharers_job);
+  long workers = c->sched_grid > 0 ? c->sched_grid : (long)std::min<size_t>(tiles, (size_t)job_cap);
+  workers = std::max<long>(1, std::min<long>(workers, kStepSlots));
+  nchan = (int)std::max<long>(1, std::min<long>(nchan, workers));
+  const int gx = (int)std::max<long>(1, workers / nchan);
+  sa.nchan = nchan;
+  // (worker w of a rank waits for worker w of its peer, over the same channels and pieces: the shape is part of the call)
+  sa.d.sig = sig_fold(sig_mix(sig_mix(sig_mix(a.sig, (uint64_t)nchan), (uint64_t)gx), (uint64_t)sa.pieces));
+  for (int ch = 0; ch < nchan; ch++) {
+    std::vector<int> ord;
+    ring_order(N, ch, &ord);
+    for (int i = 0; i < N; i++) sa.order[ch][i] = (uint8_t)ord[(size_t)i];
+  }
+  *gx_out = gx;
+  return traffic;
+}
+
+// one rendezvous + data movement + completion exchange: ONE kernel, or -- large messages -- meet / body / done.  A blocking call
+// learns that the collective is over from a word its closing block writes (dsync_status bytes 16..23), not from an event: set on
+// the LAST kernel of the collective only -- and not at all when a copy-out kernel behind it writes the word (host_out)
+int launch_fold(DsyncCall& call, DsyncArgs& a, const FoldStep& s, int unroll, bool last) {
+  xmpi_comm* const c = call.c;
+  ++c->dsync_epoch;  // the host's count (the kernels count for themselves, from the page: see epoch_floor)
+  if (!call.prof_events()) return XMPI_ERR_HIP;
+  memcpy(a.seg, s.seg, sizeof a.seg);
+  a.nseg = s.nseg;
+  a.host_done = last && !call.host_out ? call.done_dev : nullptr;
+  a.done_value = call.done_id;
+  const bool split = a.nseg > 0 && c->dsync_res &&
+                     (s.split_pref >= 0 ? s.split_pref != 0 : (c->dsync_split_bytes > 0 && s.moved >= (size_t)c->dsync_split_bytes));
+  RoctxRange lr("xmpi:launch %s nsrc=%d bytes=%zu epoch=%llu", split ? (c->body_sys ? "meet/body(sys)/done" : "meet/body/done") : "fold",
+                s.nsrc, s.moved, (unsigned long long)c->dsync_epoch);
+  if (split) {
+    XMPI_HIP(launch_dsync_meet(a, c->dsync_res, call.stream));
+    XMPI_HIP(launch_dsync_body(c->dsync_res, a.nseg, s.packets + 1, s.nsrc, s.dtype, s.op, s.moved, c->body_sys != 0, call.stream,
+                               call.pstart, call.pstop));
+    XMPI_HIP(launch_dsync_done(a, c->dsync_res, call.stream));
+    c->dsync_launches += 3;
+    c->dsync_split_launches++;
+    return XMPI_OK;
+  }
+  const int gx = a.nseg > 0 ? dsync_grid(c, s.packets, a.nseg, unroll) : 1;
+  XMPI_HIP(launch_dsync_fold(a, s.nsrc, s.dtype, s.op, gx, unroll, call.stream, call.pstart, call.pstop));
+  c->dsync_launches++;
+  return XMPI_OK;
+}
+
+int launch_sched(DsyncCall& call, DsyncSchedArgs& sa, int gx, int dtype, int op) {
+  xmpi_comm* const c = call.c;
+  ++c->dsync_epoch;
+  if (!call.prof_events()) return XMPI_ERR_HIP;
+  sa.d.host_done = call.host_out ? nullptr : call.done_dev;
+  sa.d.done_value = call.done_id;
+  RoctxRange lr("xmpi:launch sched=%d channels=%d workers=%d pieces=%d epoch=%llu", sa.sched, sa.nchan, gx, sa.pieces,
+                (unsigned long long)c->dsync_epoch);
+  XMPI_HIP(launch_dsync_sched(sa, dtype, op, gx, call.stream, call.pstart, call.pstop));
+  c->dsync_launches++;
+  c->dsync_sched_launches++;
+  return XMPI_OK;
+}
+
+// Buffers the peers can map.  Anything else -- host memory, device memory that was never registered -- is stood in for by a block
+// of a registered arena (one local copy in, one out); the collective itself is the same zero-copy exchange.  Also where the result
+// of a stand-in goes home from, and how.  A failure is the call's (DsyncCall::fail), but under capture, which lends nothing.
+int resolve_buffers(DsyncCall& call, const CollArgs& k, const DsyncRoute& rt, const void* sendbuf, void* recvbuf, bool capturing, Resolved* r) {
+  xmpi_comm* const c = call.c;
+  const int N = c->size, me = c->rank, coll = k.coll;
+  const bool recv_significant = coll != COLL_REDUCE || me == k.root;
+  const bool in_place = sendbuf == recvbuf;
   // a capture bakes addresses into the graph: a stand-in would be given back to the arena while replays still use it
-  auto no_standin = [&]() {
+  auto no_standin = [] {
     set_last_error("graph capture needs registered device buffers (xmpi_malloc / xmpi_register)");
     return XMPI_ERR_ARG;
   };
-  if (!zc_export(c, r.send, send_bytes, &r.sref)) {
+  int rc = XMPI_OK;
+  r->send = sendbuf;
+  r->recv = recv_significant ? recvbuf : const_cast<void*>(sendbuf);
+  if (!zc_export(c, r->send, k.send_bytes, &r->sref)) {
     if (capturing) return no_standin();
-    r.tmp_send = heap_alloc(c->device, send_bytes);
-    if (!r.tmp_send) return fail(XMPI_ERR_NOMEM);
-    lent.push_back(r.tmp_send);
-    if (coll != COLL_BCAST || me == root) {
+    r->tmp_send = lend_standin(c, call.lent, k.send_bytes, &r->sref, &rc);
+    if (!r->tmp_send) return call.fail(rc);
+    if (coll != COLL_BCAST || me == k.root) {
       // a host slice of a blocking call goes in through pinned memory the GPU reads itself (memcpy + one small kernel in
       // stream order) -- the runtime's copy out of pageable memory is a staged, synchronous affair of 10 us and more
-      if (blocking && send_bytes <= xmpi_comm::kHostBounce && c->p2p_tickets && !is_device_pointer(sendbuf) && host_bounce_ready(c)) {
-        memcpy(c->host_bounce, sendbuf, send_bytes);
-        DS_HIP(bounce_copy(c, r.tmp_send, c->host_bounce_dev, send_bytes, 0, nullptr, 0, stream));
-        c->host_bounce_calls++;
-      } else {
-        DS_HIP(hipMemcpyAsync(r.tmp_send, sendbuf, send_bytes, hipMemcpyDefault, stream));
-      }
+      const bool pinned = call.blocking && k.send_bytes <= xmpi_comm::kHostBounce && c->p2p_tickets && !is_device_pointer(sendbuf) &&
+                          host_bounce_ready(c);
+      if (pinned) memcpy(c->host_bounce, sendbuf, k.send_bytes);
+      const hipError_t e = pinned ? bounce_copy(c, r->tmp_send, c->host_bounce_dev, k.send_bytes, 0, nullptr, 0, call.stream)
+                                  : hipMemcpyAsync(r->tmp_send, sendbuf, k.send_bytes, hipMemcpyDefault, call.stream);
+      if (e != hipSuccess) return call.fail(hip_fail(e, "copy into a stand-in", __FILE__, __LINE__));
+      if (pinned) c->host_bounce_calls++;
     }
-    r.send = r.tmp_send;
-    if (!zc_export(c, r.send, send_bytes, &r.sref)) return fail(XMPI_ERR_HIP);
-    c->dsync_bounced++;
+    r->send = r->tmp_send;
   }
   if (!recv_significant || (in_place && coll != COLL_ALLGATHER)) {
-    r.recv = const_cast<void*>(r.send);
-    r.rref = r.sref;
-  } else if (!zc_export(c, r.recv, recv_bytes, &r.rref)) {
+    r->recv = const_cast<void*>(r->send);
+    r->rref = r->sref;
+  } else if (!zc_export(c, r->recv, k.recv_bytes, &r->rref)) {
     if (capturing) return no_standin();
-    r.tmp_recv = heap_alloc(c->device, recv_bytes);
-    if (!r.tmp_recv) return fail(XMPI_ERR_NOMEM);
-    lent.push_back(r.tmp_recv);
-    r.recv = r.tmp_recv;
-    if (!zc_export(c, r.recv, recv_bytes, &r.rref)) return fail(XMPI_ERR_HIP);
-    c->dsync_bounced++;
+    r->tmp_recv = lend_standin(c, call.lent, k.recv_bytes, &r->rref, &rc);
+    if (!r->tmp_recv) return call.fail(rc);
+    r->recv = r->tmp_recv;
   }
-
-  // The communicator KEEPS one registered block for what a stepped collective needs beside the caller's buffers -- the push forms'
-  // landing block, the pull-form tree reduce's accumulator -- and uses it again for the next one (grown when one needs more): the
-  // peers touch it only between this rank's announce for a collective and its close, and its kernels run one at a time -- so
-  // back-to-back enqueued collectives share one block, where a block lent per call would have each of them take a new one before
-  // the stream has given the last one back (1 GiB fp16, halving push form, 5 enqueued steps: a new 1 GiB arena allocated,
-  // exported and mapped by every peer per step -- 100 ms instead of 9).
-  auto own_block = [&](size_t bytes) -> void* {
-    if (!c->land_block || c->land_block_bytes < bytes) {
-      // the outgrown block goes back once THIS collective's kernel -- behind every earlier one -- has passed.  Not through `lent`:
-      // a failure path gives `lent` back at once, and earlier ENQUEUED collectives may still be landing in this block
-      if (c->land_block) outgrown.push_back(c->land_block);
-      c->land_block = heap_alloc(c->device, bytes);
-      c->land_block_bytes = c->land_block ? bytes : 0;
-    }
-    return c->land_block;
-  };
   // binary-tree reduce, pull form: an inner node that is not the root accumulates its subtree's partial result in a block the
-  // parent can read (sched_steps.h SCHED_TREE_REDUCE); the caller's receive buffer means nothing there
-  if (stepped && !sched_push && coll == COLL_REDUCE && me != root && 2 * ((me - root + N) % N) + 1 < N) {
-    if (capturing) return no_standin();
-    void* acc = own_block(send_bytes);
-    if (!acc) return fail(XMPI_ERR_NOMEM);
-    r.recv = acc;
-    if (!zc_export(c, r.recv, send_bytes, &r.rref)) return fail(XMPI_ERR_HIP);
+  // parent can read (sched_steps.h SCHED_TREE_REDUCE); the caller's receive buffer means nothing there.  (Never under capture:
+  // the route runs a captured tree reduce as the fold.)
+  if (rt.form == DsyncRoute::STEPPED && !rt.sched_push && coll == COLL_REDUCE && me != k.root && 2 * ((me - k.root + N) % N) + 1 < N) {
+    r->recv = call.own_block(k.send_bytes);
+    if (!r->recv) return call.fail(XMPI_ERR_NOMEM);
+    if (!zc_export(c, r->recv, k.send_bytes, &r->rref)) return call.fail(XMPI_ERR_HIP);
   }
+  // where the result of a stand-in goes home from, and how: a host slice of a blocking call comes out through pinned memory --
+  // one more small kernel in stream order copies the stand-in there and THEN writes the completion word
+  call.out_src = r->tmp_recv ? r->tmp_recv
+                 : (r->tmp_send && recv_significant && (in_place || coll == COLL_BCAST) && coll != COLL_ALLGATHER) ? r->tmp_send
+                                                                                                                   : nullptr;
+  call.host_out = call.blocking && call.out_src && k.recv_bytes <= xmpi_comm::kHostBounce && c->p2p_tickets && c->dsync_status_dev &&
+                  !is_device_pointer(recvbuf) && host_bounce_ready(c);
+  return XMPI_OK;
+}
 
-  // where the result of a stand-in goes home from (step 4), and how: a host slice of a blocking call comes out through pinned
-  // memory -- one more small kernel in stream order copies the stand-in there and THEN writes the completion word
-  const void* out_src = r.tmp_recv ? r.tmp_recv
-                        : (r.tmp_send && recv_significant && (in_place || coll == COLL_BCAST) && coll != COLL_ALLGATHER) ? r.tmp_send
-                                                                                                                          : nullptr;
-  const bool host_out = blocking && out_src && recv_bytes <= xmpi_comm::kHostBounce && c->p2p_tickets && c->dsync_status_dev &&
-                        !is_device_pointer(recvbuf) && host_bounce_ready(c);
+// the peers know the allocations: both buffers are published, and every peer has mapped them
+int announce(xmpi_comm* c, const Resolved& r, bool capturing, int* sslot, int* rslot) {
+  uint64_t ps = 0, pr = 0;
+  int rc = publish(c, r.sref, sslot, &ps, capturing);
+  if (rc == XMPI_OK) rc = publish(c, r.rref, rslot, &pr, capturing);
+  if (rc == XMPI_OK) rc = await_acks(c, std::max(ps, pr));
+  return rc;
+}
 
-  // 2. the peers know the allocations
-  int sslot = 0, rslot = 0;
-  uint64_t need = 0, pi = 0;
-  int rc = publish(c, r.sref, &sslot, &pi, capturing);
-  if (rc) return fail(rc);
-  need = std::max(need, pi);
-  rc = publish(c, r.rref, &rslot, &pi, capturing);
-  if (rc) return fail(rc);
-  need = std::max(need, pi);
-  rc = await_acks(c, need);
-  if (rc) return fail(rc);
+// ... and the communicator's landing block (DsyncCall::own_block) a push form's peers store into: into d's land_* fields
+int announce_land(DsyncCall& call, size_t bytes, bool capturing, DsyncArgs* d) {
+  void* const own = call.own_block(bytes);
+  if (!own) return XMPI_ERR_NOMEM;
+  BufRef lref;
+  if (!zc_export(call.c, own, bytes, &lref)) return XMPI_ERR_HIP;
+  int slot = 0;
+  uint64_t pi = 0;
+  int rc = publish(call.c, lref, &slot, &pi, capturing);
+  if (rc == XMPI_OK) rc = await_acks(call.c, pi);
+  if (rc != XMPI_OK) return rc;
+  d->land_gen = lref.gen;
+  d->land_off = lref.offset;
+  d->land_slot = (uint64_t)slot;
+  d->my_land = own;
+  return XMPI_OK;
+}
 
-  rc = order_behind_last(c, stream, capturing);
-  if (rc) return fail(rc);
-
-  // 3. the kernel(s)
+// what every kernel of the collective is told: the pages, this rank's announced buffers, where it reports
+DsyncArgs meet_args(const xmpi_comm* c, const Resolved& r, int sslot, int rslot) {
   DsyncArgs a;
   memset(&a, 0, sizeof a);
-  for (int p = 0; p < N; p++) a.page[p] = c->peer_page[p];
-  a.me = me;
-  a.n = N;
+  for (int p = 0; p < c->size; p++) a.page[p] = c->peer_page[p];
+  a.me = c->rank;
+  a.n = c->size;
   a.send_gen = r.sref.gen;
   a.send_off = r.sref.offset;
   a.send_slot = (uint64_t)sslot;
@@ -1124,336 +1461,90 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   a.tag = c->dsync_tag;
   a.epoch_floor = c->dsync_base;
   a.host_epoch = c->dsync_status_dev ? (uint64_t*)(c->dsync_status_dev + 2) : nullptr;
-  // a blocking call learns that the collective is over from a word its closing block writes (dsync_status bytes 16..23),
-  // not from an event: set on the LAST kernel of the collective only (below)
-  const uint64_t done_id = ++c->dsync_done_seq;
-  uint64_t* const done_dev = (blocking && c->dsync_status_dev) ? (uint64_t*)(c->dsync_status_dev + 4) : nullptr;
-  uint64_t* const done_k = host_out ? nullptr : done_dev;  // (host_out: the copy-out kernel behind the collective writes it)
   a.my_send = r.send;
   a.my_recv = r.recv;
   a.abort_word = c->dsync_abort_dev;
   a.status = c->dsync_status_dev;
   a.xcc_need = (c->xcd_check && !c->body_sys) ? c->xcds : 0;  // (body_sys: the data kernel needs no L2 to have been acquired)
   a.spin_limit = c->timeout_s > 0 ? (uint64_t)c->timeout_s * 100000000ull : 0;  // wall_clock64 ticks at 100 MHz
-  const uint32_t everyone = N >= 32 ? 0xffffffffu : ((1u << N) - 1u);
-  const size_t al = std::max<size_t>(1, 16 / es);
+  return a;
+}
 
-  hipEvent_t pstart = nullptr, pstop = nullptr;
-  // sampled launches carry their own begin / end events (attached to the dispatch); a launch that is only enqueued
-  // leaves them for the next blocking call to read, so sampling does not put a host wait between enqueued steps
-  const bool sampled = !capturing && c->prof_on && (c->prof_seq[PROF_ZCOPY]++ % (uint64_t)std::max<long>(1, c->prof_every)) == 0;
-  size_t traffic = 0;
-  auto prof_events = [&]() -> bool {
-    if (sampled && !pstart) {
-      pstart = ev_get(c, true);
-      pstop = ev_get(c, true);
-      if (!pstart || !pstop) return false;
-    }
-    return true;
-  };
-  // one rendezvous + data movement + completion exchange: ONE kernel, or -- large messages -- meet / body / done
-  auto launch = [&](int nsrc, int kdtype, int kop, size_t packets, size_t bytes_moved, bool last = true) -> int {
-    ++c->dsync_epoch;  // the host's count (the kernels count for themselves, from the page: see epoch_floor)
-    if (!prof_events()) return XMPI_ERR_HIP;
-    a.host_done = last ? done_k : nullptr;
-    a.done_value = done_id;
-    const bool split = a.nseg > 0 && c->dsync_res &&
-                       (split_pref >= 0 ? split_pref != 0 : (c->dsync_split_bytes > 0 && bytes_moved >= (size_t)c->dsync_split_bytes));
-    RoctxRange lr("xmpi:launch %s nsrc=%d bytes=%zu epoch=%llu", split ? (c->body_sys ? "meet/body(sys)/done" : "meet/body/done") : "fold",
-                  nsrc, bytes_moved, (unsigned long long)c->dsync_epoch);
-    if (split) {
-      XMPI_HIP(launch_dsync_meet(a, c->dsync_res, stream));
-      XMPI_HIP(launch_dsync_body(c->dsync_res, a.nseg, packets + 1, nsrc, kdtype, kop, bytes_moved, c->body_sys != 0, stream,
-                                 sampled ? pstart : nullptr, sampled ? pstop : nullptr));
-      XMPI_HIP(launch_dsync_done(a, c->dsync_res, stream));
-      c->dsync_launches += 3;
-      c->dsync_split_launches++;
-      return XMPI_OK;
-    }
-    const int gx = a.nseg > 0 ? dsync_grid(c, packets, a.nseg, unroll) : 1;
-    XMPI_HIP(launch_dsync_fold(a, nsrc, kdtype, kop, gx, unroll, stream, sampled ? pstart : nullptr, sampled ? pstop : nullptr));
-    c->dsync_launches++;
-    return XMPI_OK;
-  };
+}  // namespace
 
-  // (under capture the push-only form is the fold: its staging area is a block the communicator may replace later)
-  const bool use_push = push && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE) && !capturing;
-  // What this call is, for the peers to compare with theirs (kdev.h dsync_begin): ranks that are not in the same collective, on the
-  // same schedule, over the same bytes end with an error before any of them has touched another's memory -- instead of a hang, or
-  // of a fold over buffers of different lengths.  (One kernel or meet / body / done is NOT part of it: those mix.)
-  {
-    const bool reduces = coll == COLL_ALLREDUCE || coll == COLL_REDUCE, rooted = coll == COLL_BCAST || coll == COLL_REDUCE;
-    const uint64_t form = stepped ? 16u + 2u * (uint64_t)sched_algo + (sched_push ? 1u : 0u)
-                          : use_push ? 2u
-                          : (coll == COLL_BCAST && !(N <= 2 || send_bytes <= (size_t)std::max<long>(0, c->zc_bcast_push_bytes))) ? 3u : 1u;
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    for (uint64_t v : {(uint64_t)coll + 1, form, (uint64_t)send_bytes, reduces ? (uint64_t)dtype + 1 : 0, reduces ? (uint64_t)op + 1 : 0,
-                       rooted ? (uint64_t)root + 1 : 0})
-      h = sig_mix(h, v);
-    a.sig = sig_fold(h);
-  }
-  if (stepped) {
-    // ring / recursive halving + doubling / binary tree: ONE kernel per rank runs every step of the schedule, the steps
-    // released by flag words between the peers' kernels (sched.hip) -- the schedules north_star names, without a host
-    // between their steps
+// One device-synchronised collective, enqueued on `stream`.  blocking: wait for it (the xmpi_allreduce family);
+// otherwise return once it is enqueued (xmpi_*_on_stream).  Every rank of the job takes this path for the same
+// calls (the decision depends on the communicator and the arguments only), so the epochs agree.
+int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,
+                     int op, hipStream_t stream, bool blocking, int algo) {
+  const size_t es = xmpi_dtype_size((xmpi_dtype)dtype);
+  const CollArgs k{coll, root, dtype, op, count, es, count * es, count * es * (coll == COLL_ALLGATHER ? (size_t)c->size : 1)};
+  if (!stream) stream = c->local_stream;
+  DsyncCall call(c, stream, blocking);
+  dsync_service(c);
+  reap_deferred(c, false);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(stream, &cap);
+  (void)hipGetLastError();
+  const bool capturing = cap != hipStreamCaptureStatusNone;
+
+  // route: a refused call and an LL call end here
+  const DsyncRoute rt = dsync_route(c, coll, algo, k.send_bytes, capturing);
+  if (rt.refused >= 0) return refuse(coll, rt.refused);
+  if (rt.form == DsyncRoute::LL) return dsync_ll(call, k, sendbuf, recvbuf, capturing);
+  RoctxRange range("xmpi:dsync %s algo=%s bytes=%zu epoch=%llu %s", coll_name(coll), algo_name(rt.algo), k.send_bytes,
+                   (unsigned long long)c->dsync_epoch + 1, blocking ? "blocking" : capturing ? "captured" : "enqueued");
+
+  // resolve the buffers, announce them
+  Resolved r;
+  int rc = resolve_buffers(call, k, rt, sendbuf, recvbuf, capturing, &r);
+  if (rc != XMPI_OK) return rc;
+  int sslot = 0, rslot = 0;
+  rc = announce(c, r, capturing, &sslot, &rslot);
+  if (rc == XMPI_OK) rc = order_behind_last(c, stream, capturing);
+  if (rc != XMPI_OK) return call.fail(rc);
+
+  // build and launch the kernel(s)
+  call.begin(capturing);
+  DsyncArgs a = meet_args(c, r, sslot, rslot);
+  a.sig = call_sig(c, k, rt);
+  if (rt.form == DsyncRoute::STEPPED) {
     DsyncSchedArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.d = a;
-    sa.root = root;
-    sa.count = count;
-    sa.elem_size = (uint32_t)es;
-    sa.pieces = 1;
-    sa.push = sched_push ? 1u : 0u;
-    size_t step_bytes = send_bytes;  // what the largest step of the schedule moves
-    int nchan = 1;
-    if (sched_algo == XMPI_ALGO_RING) {
-      sa.sched = coll == COLL_ALLREDUCE ? SCHED_RING_ALLREDUCE : SCHED_RING_ALLGATHER;
-      step_bytes = coll == COLL_ALLREDUCE ? (send_bytes + (size_t)N - 1) / (size_t)N : send_bytes;
-      // every channel is a different cyclic order of the ranks (plan.cpp ring_order: on an even mesh N-2 directed rings
-      // that share no link direction); ranks sharing a GPU have no links to spread over
-      const int avail = std::min(ring_channel_count(N), kMaxSchedChannels);
-      // (the shape of a stepped kernel -- channels, workers -- is protocol: worker w waits for worker w of its peer.  It follows
-      // the job's most crowded GPU, which every rank reads alike, not this rank's own: 5 ranks on 2 GPUs sit 3 + 2)
-      nchan = c->sched_channels > 0 ? (int)std::min<long>(c->sched_channels, avail) : (c->dsync_sharers_job > 1 ? 1 : avail);
-      // (reduce-scatter 2 reads + 1 write per step, allgather 1 + 1; the push form reads its own first chunk once more)
-      traffic = coll == COLL_ALLREDUCE ? (5 * (size_t)(N - 1) + (sched_push ? 1 : 0)) * step_bytes : 2 * (size_t)N * send_bytes;
-    } else if (sched_algo == XMPI_ALGO_RHD) {
-      sa.sched = SCHED_RHD_ALLREDUCE;
-      step_bytes = send_bytes / 2;
-      // halving: 3 x (S/2 + S/4 + ...), doubling: 2 x the same; push form: the landing regions are written and read -- one more
-      traffic = (sched_push ? 6 : 5) * (send_bytes - send_bytes / (size_t)N);
-      if ((N & (N - 1)) != 0) traffic += 3 * send_bytes;     // (no power of two: the fold-in / fold-out steps, at most)
-    } else {
-      sa.sched = coll == COLL_BCAST ? SCHED_TREE_BCAST : SCHED_TREE_REDUCE;
-      const size_t piece = (size_t)std::max<long>(4096, c->tree_piece_bytes);
-      sa.pieces = (int)std::min<size_t>(32, std::max<size_t>(1, (send_bytes + piece - 1) / piece));
-      step_bytes = (send_bytes + (size_t)sa.pieces - 1) / (size_t)sa.pieces;
-      const int v = (me - root + N) % N;
-      const size_t children = (size_t)((2 * v + 1 < N) + (2 * v + 2 < N));
-      if (coll == COLL_BCAST) {  // pull: a node reads its parent's piece and writes its own; push: it reads its own and writes each child's
-        traffic = sched_push ? 2 * send_bytes * children : (me == root ? 0 : 2 * send_bytes);
-      } else {  // pull: 2 reads + 1 write per child; push: own input + one slot per child read, one buffer stored (upwards, or the result)
-        traffic = sched_push ? (children + 2) * send_bytes : 3 * send_bytes * children;
-      }
-    }
+    int gx = 1;
+    call.traffic = plan_sched(c, k, rt, a, &sa, &gx);
     // push form: the block the peers store into where this rank's receive buffer cannot take their data yet (sched_steps.h
     // sched_land_bytes: in-place ring allreduce -- the receive buffer still is the input; halving -- a region per level; tree
-    // reduce -- a slot per child).  Lent per call from the registered arenas: the peers have mapped those long ago.
-    sa.d.me = me;
-    sa.d.n = N;
-    const size_t land_bytes = (size_t)sched_land_bytes(sa, r.send == r.recv);
-    c->dsync_land_bytes = land_bytes;
-    if (land_bytes) {
-      if (capturing) return no_standin();
-      void* const own = own_block(land_bytes);
-      if (!own) return fail(XMPI_ERR_NOMEM);
-      void* land = own;
-      BufRef lref;
-      if (!zc_export(c, land, land_bytes, &lref)) return fail(XMPI_ERR_HIP);
-      int lslot = 0;
-      rc = publish(c, lref, &lslot, &pi, capturing);
-      if (rc == XMPI_OK) rc = await_acks(c, pi);
-      if (rc) return fail(rc);
-      sa.d.land_gen = lref.gen;
-      sa.d.land_off = lref.offset;
-      sa.d.land_slot = (uint64_t)lslot;
-      sa.d.my_land = land;
+    // reduce -- a slot per child).  (Never under capture: the route runs a captured push form as its pull form.)
+    const size_t land = (size_t)sched_land_bytes(sa, r.send == r.recv);
+    c->dsync_land_bytes = land;
+    if (land) rc = announce_land(call, land, capturing, &sa.d);
+    if (rc == XMPI_OK) rc = launch_sched(call, sa, gx, dtype, op);
+  } else {
+    const FoldPlan p = rt.form == DsyncRoute::PUSH_ONLY        ? plan_push_only(c, k)
+                       : coll == COLL_ALLGATHER                ? plan_allgather(c, k, rt.split_pref)
+                       : coll != COLL_BCAST                    ? plan_fold(c, k, rt.split_pref)
+                       : bcast_forwards(c, k.send_bytes)       ? plan_bcast_forward(c, k)
+                                                               : plan_bcast_push(c, k);
+    if (p.land) {
+      rc = announce_land(call, p.land, capturing, &a);
+      if (rc == XMPI_OK) c->dsync_land_bytes = p.land;
     }
-    const size_t tiles = std::max<size_t>(1, (step_bytes + kSchedTileBytes - 1) / kSchedTileBytes);
-    const long job_cap = c->dsync_grid_cap > 0 ? c->dsync_grid_cap : 1024 / std::max(1, c->dsync_sharers_job);
-    long workers = c->sched_grid > 0 ? c->sched_grid : (long)std::min<size_t>(tiles, (size_t)job_cap);
-    workers = std::max<long>(1, std::min<long>(workers, kStepSlots));
-    nchan = (int)std::max<long>(1, std::min<long>(nchan, workers));
-    const int gx = (int)std::max<long>(1, workers / nchan);
-    sa.nchan = nchan;
-    // (worker w of a rank waits for worker w of its peer, over the same channels and pieces: the shape is part of the call)
-    sa.d.sig = sig_fold(sig_mix(sig_mix(sig_mix(a.sig, (uint64_t)nchan), (uint64_t)gx), (uint64_t)sa.pieces));
-    for (int ch = 0; ch < nchan; ch++) {
-      std::vector<int> ord;
-      ring_order(N, ch, &ord);
-      for (int i = 0; i < N; i++) sa.order[ch][i] = (uint8_t)ord[(size_t)i];
-    }
-    ++c->dsync_epoch;
-    if (!prof_events()) return fail(XMPI_ERR_HIP);
-    sa.d.host_done = done_k;
-    sa.d.done_value = done_id;
-    {
-      RoctxRange lr("xmpi:launch sched=%d channels=%d workers=%d pieces=%d epoch=%llu", sa.sched, nchan, gx, sa.pieces,
-                    (unsigned long long)c->dsync_epoch);
-      DS_HIP(launch_dsync_sched(sa, dtype, op, gx, stream, sampled ? pstart : nullptr, sampled ? pstop : nullptr));
-    }
-    c->dsync_launches++;
-    c->dsync_sched_launches++;
-    rc = XMPI_OK;
-  } else if (use_push) {
-    // Push-only (XMPI_ALGO_ZPUSH): the fold with nothing READ over xGMI -- loads over a link are round trips, stores are posted.
-    // Two device-synchronised kernels: every rank stores its contribution to chunk q into region `me` of rank q's own block
-    // (own_block: the communicator's staging area, announced with the buffers; chunks cut as the fold cuts them, zc_chunk --
-    // so in place and ragged counts work like anything else); then, all of chunk `me` being local, folds it in rank order and
-    // stores the result into its place in everybody's receive buffer.  One hop each way, S / N per link direction and kernel.
-    size_t maxc = 0;
-    for (int q = 0; q < N; q++) {
-      size_t off = 0, cnt = 0;
-      zc_chunk(count, es, N, q, &off, &cnt);
-      maxc = std::max(maxc, cnt * es);
-    }
-    const size_t region = (maxc + 255) / 256 * 256;
-    void* const own = own_block(region * (size_t)N);
-    if (!own) return fail(XMPI_ERR_NOMEM);
-    BufRef lref;
-    if (!zc_export(c, own, region * (size_t)N, &lref)) return fail(XMPI_ERR_HIP);
-    int lslot = 0;
-    rc = publish(c, lref, &lslot, &pi, capturing);
-    if (rc == XMPI_OK) rc = await_acks(c, pi);
-    if (rc) return fail(rc);
-    a.land_gen = lref.gen;
-    a.land_off = lref.offset;
-    a.land_slot = (uint64_t)lslot;
-    a.my_land = own;
-    c->dsync_land_bytes = region * (size_t)N;
-    split_pref = 0;
-    size_t my_off = 0, my_cnt = 0, maxp = 0;
-    zc_chunk(count, es, N, me, &my_off, &my_cnt);
-    for (int q = 0; q < N; q++) {
-      size_t off = 0, cnt = 0;
-      zc_chunk(count, es, N, q, &off, &cnt);
-      if (q == me || cnt == 0) continue;
-      DsyncSeg& g = a.seg[a.nseg++];
-      g.src_off = off * es;             // my contribution to chunk q ...
-      g.dst_off = (size_t)me * region;  // ... into region `me` of rank q's block
-      g.count = cnt * es;
-      g.src_mask = 1u << me;
-      g.dst_mask = 1u << q;
-      g.dst_to_land = 1;
-      maxp = std::max(maxp, cnt * es / 16);
-      traffic += 2 * cnt * es;
-    }
-    rc = launch(1, XMPI_U8, XMPI_SUM, maxp, traffic, /*last=*/false);
-    if (rc == XMPI_OK) {
-      // every contribution to chunk `me` is local now (the first kernel's close: every peer's stores have landed): ONE more kernel
-      // folds them in rank order and stores the result into its place in everybody's receive buffer -- the fold's own kernels
-      // (one kernel, or meet / body / done by size) with local sources.  Its rendezvous doubles as "my buffers may be written";
-      // nobody's block is written again before its owner's next collective has announced it.
-      memset(a.seg, 0, sizeof a.seg);
-      a.nseg = my_cnt > 0 ? 1 : 0;
-      a.seg[0].src_off = a.seg[0].dst_off = my_off * es;
-      a.seg[0].count = my_cnt;
-      a.seg[0].src_mask = everyone;
-      a.seg[0].src_from_recv = 2;
-      a.seg[0].stage_stride = region;
-      a.seg[0].dst_mask = coll == COLL_REDUCE ? (1u << root) : everyone;  // (reduce: the folded chunks meet in the root's buffer)
-      split_pref = -1;  // (meet / body / done by size, like the fold it is)
-      const size_t moved = (size_t)(N + (coll == COLL_REDUCE ? 1 : N)) * my_cnt * es;
-      traffic += moved;
-      rc = launch(N, dtype, op, my_cnt / al, moved);
-    }
-  } else if (coll == COLL_ALLREDUCE || coll == COLL_REDUCE) {
-    size_t off = 0, cnt = 0;
-    zc_chunk(count, es, N, me, &off, &cnt);
-    a.nseg = cnt > 0 ? 1 : 0;
-    a.seg[0].src_off = a.seg[0].dst_off = off * es;
-    a.seg[0].count = cnt;
-    a.seg[0].src_mask = everyone;
-    a.seg[0].dst_mask = coll == COLL_REDUCE ? (1u << root) : everyone;
-    traffic = (size_t)(N + (coll == COLL_REDUCE ? 1 : N)) * cnt * es;
-    rc = launch(N, dtype, op, cnt / al, traffic);
-  } else if (coll == COLL_ALLGATHER) {
-    a.nseg = 1;
-    a.seg[0].src_off = 0;
-    a.seg[0].dst_off = (size_t)me * send_bytes;
-    a.seg[0].count = send_bytes;
-    a.seg[0].src_mask = 1u << me;
-    a.seg[0].dst_mask = everyone;
-    traffic = (size_t)(1 + N) * send_bytes;
-    rc = launch(1, XMPI_U8, XMPI_SUM, send_bytes / 16, traffic);
-  } else {  // COLL_BCAST: `send` and `recv` are the same buffer on every rank
-    const bool root_pushes = N <= 2 || send_bytes <= (size_t)std::max<long>(0, c->zc_bcast_push_bytes);
-    if (root_pushes) {  // the root stores into every buffer; the others only take part in the rendezvous
-      a.nseg = me == root ? 1 : 0;
-      a.seg[0].count = send_bytes;
-      a.seg[0].src_mask = 1u << root;
-      a.seg[0].dst_mask = everyone & ~(1u << root);
-      traffic = me == root ? (size_t)N * send_bytes : 0;
-      split_pref = 0;  // (the ranks differ in what they launch: keep to the one-kernel form, whose shape does not matter)
-      rc = launch(1, XMPI_U8, XMPI_SUM, send_bytes / 16, traffic);
-    } else {
-      // the root scatters chunk j to rank j (one segment per destination, each over its own link), then every
-      // rank forwards its chunk to the others: each link carries S/N twice instead of the root's links carrying S
-      size_t maxp = 0;
-      split_pref = 0;
-      if (me == root) {
-        for (int j = 0; j < N; j++) {
-          size_t off = 0, cnt = 0;
-          zc_chunk(count, es, N, j, &off, &cnt);
-          if (j == root || cnt == 0) continue;
-          DsyncSeg& g = a.seg[a.nseg++];
-          g.src_off = g.dst_off = off * es;
-          g.count = cnt * es;
-          g.src_mask = 1u << root;
-          g.dst_mask = 1u << j;
-          maxp = std::max(maxp, cnt * es / 16);
-          traffic += 2 * cnt * es;
-        }
-      }
-      rc = launch(1, XMPI_U8, XMPI_SUM, maxp, traffic, /*last=*/false);
-      if (rc == XMPI_OK) {
-        memset(a.seg, 0, sizeof a.seg);
-        size_t off = 0, cnt = 0;
-        zc_chunk(count, es, N, me, &off, &cnt);
-        a.nseg = cnt > 0 ? 1 : 0;
-        a.seg[0].src_off = a.seg[0].dst_off = off * es;
-        a.seg[0].count = cnt * es;
-        a.seg[0].src_mask = 1u << me;
-        a.seg[0].dst_mask = everyone & ~(1u << me) & ~(1u << root);
-        traffic += (size_t)(N - 1) * cnt * es;
-        rc = launch(1, XMPI_U8, XMPI_SUM, cnt * es / 16, (size_t)(N - 1) * cnt * es);
-      }
+    for (int i = 0; rc == XMPI_OK && i < p.kernels; i++) {
+      call.traffic += p.k[i].moved;
+      rc = launch_fold(call, a, p.k[i], rt.unroll, i + 1 == p.kernels);
     }
   }
-  if (rc != XMPI_OK) return fail(rc);
+  if (rc != XMPI_OK) return call.fail(rc);
   if (!capturing) c->dsync_last_stream = stream;
-
-  if (host_out) {
-    DS_HIP(bounce_copy(c, c->host_bounce_dev + xmpi_comm::kHostBounce, out_src, recv_bytes, 1, done_dev, done_id, stream));
+  if (call.host_out) {
+    const hipError_t e = bounce_copy(c, c->host_bounce_dev + xmpi_comm::kHostBounce, call.out_src, k.recv_bytes, 1, call.done_dev,
+                                     call.done_id, stream);
+    if (e != hipSuccess) return call.fail(hip_fail(e, "copy of a stand-in's result into pinned memory", __FILE__, __LINE__));
     c->host_bounce_calls++;
   }
 
-  // 4. results of a stand-in go home; stand-ins go back to the arena when the stream has passed them.
-  //    (A copy into pageable host memory blocks the calling thread until the kernel before it has ended -- and the
-  //    kernel ends only when every peer has arrived, which a peer may be unable to do before THIS rank has mapped a
-  //    buffer it just registered.  So a blocking call copies out after its polling wait below, which serves the
-  //    peers; the stream-ordered forms take device memory only, where the copy really is asynchronous.)
-  if (!blocking) {
-    if (pstart) c->dsync_prof_pending.push_back({pstart, pstop, traffic});
-    if (out_src) DS_HIP(hipMemcpyAsync(recvbuf, out_src, recv_bytes, hipMemcpyDeviceToDevice, stream));
-    lent.insert(lent.end(), outgrown.begin(), outgrown.end());
-    outgrown.clear();
-    if (!lent.empty()) {
-      xmpi_comm::DsyncDeferred d;
-      if (hipEventCreateWithFlags(&d.done, hipEventDisableTiming) != hipSuccess) return fail(XMPI_ERR_HIP);
-      DS_HIP(hipEventRecord(d.done, stream));
-      d.bufs = lent;
-      c->dsync_deferred.push_back(d);
-    }
-    return XMPI_OK;
-  }
-
-  rc = wait_blocking(c, stream, done_dev != nullptr, done_id);
-  if (rc != XMPI_OK) return fail(rc);
-  lent.insert(lent.end(), outgrown.begin(), outgrown.end());  // (the stream has passed this collective, and with it every earlier one)
-  outgrown.clear();
-  if (c->api_calls.load(std::memory_order_relaxed) == calls_at_entry) c->agent_quiet_at = calls_at_entry;  // (as in dsync_ll: the next blocking small collective need not ask the streams)
-  if (host_out) {
-    memcpy(recvbuf, c->host_bounce + xmpi_comm::kHostBounce, recv_bytes);
-  } else if (out_src) {
-    DS_HIP(hipMemcpyAsync(recvbuf, out_src, recv_bytes, hipMemcpyDefault, stream));
-    DS_HIP(hipStreamSynchronize(stream));
-  }
-  for (void* p : lent) (void)heap_free(p);
-  lent.clear();
-  if (pstart) c->dsync_prof_pending.push_back({pstart, pstop, traffic});
-  dsync_prof_harvest(c);
-  return dsync_check(c);
+  // finish
+  return blocking ? call.wait_and_finish(recvbuf, k.recv_bytes) : call.enqueued(recvbuf, k.recv_bytes);
 }
 
 // ---- stream-ordered Send / Receive ------------------------------------------------------------------------------------
@@ -1541,20 +1632,14 @@ int dsync_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest,
   std::vector<void*> lent;
   int slot = 0;
   if (bytes > 0) {
-    const void* src = buf;
-    if (!zc_export(c, src, bytes, &ref)) {  // memory the receiver cannot map: a registered stand-in (one local copy)
-      void* tmp = heap_alloc(c->device, bytes);
-      if (!tmp) return XMPI_ERR_NOMEM;
-      lent.push_back(tmp);
-      XMPI_HIP(hipMemcpyAsync(tmp, buf, bytes, hipMemcpyDeviceToDevice, stream));
-      if (!zc_export(c, tmp, bytes, &ref)) {
-        (void)heap_free(tmp);
-        return XMPI_ERR_HIP;
-      }
-      c->dsync_bounced++;
+    int rc = XMPI_OK;
+    if (!zc_export(c, buf, bytes, &ref)) {  // memory the receiver cannot map: a registered stand-in (one local copy)
+      void* tmp = lend_standin(c, lent, bytes, &ref, &rc);
+      const hipError_t e = tmp ? hipMemcpyAsync(tmp, buf, bytes, hipMemcpyDeviceToDevice, stream) : hipSuccess;
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(stand-in)", __FILE__, __LINE__);
     }
     uint64_t pi = 0;
-    int rc = publish(c, ref, &slot, &pi);
+    if (rc == XMPI_OK) rc = publish(c, ref, &slot, &pi);
     if (rc == XMPI_OK) rc = await_acks(c, pi);
     if (rc != XMPI_OK) {
       for (void* p : lent) (void)heap_free(p);

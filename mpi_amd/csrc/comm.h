@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <condition_variable>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <map>
@@ -323,7 +324,7 @@ void zc_close_peers(const xmpi_comm* c);
 bool zc_export(xmpi_comm* c, const void* p, size_t need, BufRef* ref);
 bool zc_import(xmpi_comm* c, int peer, const BufRef& ref, void** out);
 bool registry_alive(uint64_t gen);
-// api.cpp: blocks that peers map (windows, flag pages) and the mappings of the peers' blocks are kept per
+// pool.cpp: blocks that peers map (windows, flag pages) and the mappings of the peers' blocks are kept per
 // process across communicators (exported memory is not given back by the runtime while the processes live)
 hipError_t ipc_open_shared(int owner_pid, uint64_t owner_addr, const void* handle_bytes, void** out);
 void ipc_close_shared(void* ptr);
@@ -332,6 +333,47 @@ void pool_release(void* ptr, uint64_t mark = 0);
 hipError_t pool_handle(void* ptr, void* handle_out);
 hipStream_t stream_acquire(int device);
 void stream_release(int device, hipStream_t s);
+hipStream_t shared_stream_for(int device);  // the one in-order stream of ranks that are threads of one process on one GPU
+// api.cpp
+bool trace_on();  // XMPI_TRACE=1: one line per bootstrap step on stderr (where does a rank that hangs in Init hang?)
+#define XMPI_TRACE_STEP(rank, what)                                                                          \
+  do {                                                                                                       \
+    if (::xmpi::trace_on()) fprintf(stderr, "[xmpi %d %.6f] %s\n", (rank), ::xmpi::now_seconds(), (what)); \
+  } while (0)
+long env_long(const char* name, long dflt);
+inline int use_device(const xmpi_comm* c) {
+  // HIP's current device is per OS thread and cgo moves goroutines between threads
+  XMPI_HIP(hipSetDevice(c->device));
+  return XMPI_OK;
+}
+#define XMPI_ENTER(c)                          \
+  do {                                         \
+    if (!(c) || (c)->finalized) {              \
+      ::xmpi::set_last_error("communicator not initialised"); \
+      return XMPI_ERR_STATE;                   \
+    }                                          \
+    int _rc = ::xmpi::use_device(c);           \
+    if (_rc) return _rc;                       \
+    ::xmpi::t_api_call = (c)->api_calls.fetch_add(1, std::memory_order_relaxed) + 1; \
+  } while (0)
+// no-progress limit of a steady-state wait: XMPI_TIMEOUT_S, or for ever
+inline double wait_limit(const xmpi_comm* c) { return c->timeout_s > 0 ? (double)c->timeout_s : 1e18; }
+void drain_worker(xmpi_comm* c);  // a blocking collective issued after non-blocking ones runs after them
+void stop_worker(xmpi_comm* c);
+// words the GPU writes and the host polls: pinned, mapped, zeroed (no host pointer without the allocation)
+inline void pinned_words(size_t bytes, uint64_t** host, uint64_t** dev) {
+  if (hipHostMalloc((void**)host, bytes, hipHostMallocMapped) == hipSuccess) {
+    memset(*host, 0, bytes);
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, *host, 0) == hipSuccess) *dev = (uint64_t*)d;
+  } else {
+    *host = nullptr;
+  }
+  (void)hipGetLastError();
+}
+// tune.cpp
+int job_barrier(xmpi_comm* c);
+int init_selfcheck(xmpi_comm* c);
 // dsync.cpp
 int dsync_prepare(xmpi_comm* c);
 int dsync_connect(xmpi_comm* c, double timeout_s);

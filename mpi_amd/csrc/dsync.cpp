@@ -37,8 +37,6 @@ constexpr size_t kPageBytes = kDsyncPageBytes;  // the page, the step flags of t
 
 namespace {
 
-double wait_limit(const xmpi_comm* c) { return c->timeout_s > 0 ? (double)c->timeout_s : 1e18; }
-
 void idle_hook(void* arg) { dsync_service((xmpi_comm*)arg); }
 
 }  // namespace
@@ -56,7 +54,7 @@ int dsync_prepare(xmpi_comm* c) {
     return XMPI_OK;
   };
   // uncached HBM: the page is polled by this GPU and written by the others; it must never sit in an L2.
-  // From the per-process pool (exported memory outlives communicators -- api.cpp), and NOT cleared when it is
+  // From the per-process pool (exported memory outlives communicators -- pool.cpp), and NOT cleared when it is
   // re-used: clearing is GPU work on a page seven other processes have mapped, and in a crowded GPU (eight ranks
   // plus a test runner with a context of its own) that one 64 KiB fill took 10-50 s.  Instead the epochs of the new
   // communicator start above everything an earlier one may have left in any rank's page (flag_epoch, dsync_connect).

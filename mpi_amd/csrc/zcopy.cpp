@@ -124,8 +124,6 @@ bool fill_ref(xmpi_comm* c, const void* p, size_t need, BufRef* ref, bool* fresh
   return true;
 }
 
-double tmo(const xmpi_comm* c) { return c->timeout_s > 0 ? (double)c->timeout_s : 1e18; }
-
 int count_open_fds() {
   int n = 0;
   if (DIR* d = opendir("/proc/self/fd")) {
@@ -324,7 +322,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
   }
   mine->verdict.store(0, std::memory_order_relaxed);
   mine->seq.store(seq, std::memory_order_release);
-  int rc = c->ctl->barrier(tmo(c));
+  int rc = c->ctl->barrier(wait_limit(c));
   if (rc != XMPI_OK) {
     set_last_error("zero-copy collective: a peer did not arrive");
     return rc;
@@ -394,7 +392,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
   }
   if (any_fresh) {  // new allocations were opened somewhere: agree that everybody could
     mine->verdict.store(mapped ? 1 : -1, std::memory_order_release);
-    rc = c->ctl->barrier(tmo(c));
+    rc = c->ctl->barrier(wait_limit(c));
     if (rc != XMPI_OK) return rc;
     for (int p = 0; p < N; p++)
       if (c->ctl->desc(p, seq)->verdict.load(std::memory_order_acquire) != 1) {  // staged, everywhere
@@ -439,7 +437,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
         }
       }
     }
-    rc = c->ctl->barrier(tmo(c));  // every contribution to my chunk has landed in my receive buffer
+    rc = c->ctl->barrier(wait_limit(c));  // every contribution to my chunk has landed in my receive buffer
     if (rc != XMPI_OK) return rc;
     {  // 2. fold chunk `me` in rank order: all operands are local now
       const void* srcs[kMaxRanks];
@@ -451,7 +449,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
       rc = L.finish();
       if (rc) return rc;
     }
-    rc = c->ctl->barrier(tmo(c));  // nobody still reads the staging regions my result is about to overwrite
+    rc = c->ctl->barrier(wait_limit(c));  // nobody still reads the staging regions my result is about to overwrite
     if (rc != XMPI_OK) return rc;
     {  // 3. my folded chunk -> region `me` of everybody's receive buffer
       void* dsts[kMaxRanks];
@@ -563,7 +561,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
         }
         if ((rc = flush()) != XMPI_OK) return rc;
       }
-      rc = c->ctl->barrier(tmo(c));  // chunk j has landed on rank j
+      rc = c->ctl->barrier(wait_limit(c));  // chunk j has landed on rank j
       if (rc != XMPI_OK) return rc;
       {  // allgather of the chunks: rank j forwards chunk j (the root its own) to everyone who lacks it
         size_t off = 0, cnt = 0;
@@ -586,7 +584,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
   }
 
   // 5. nobody leaves while a peer may still be reading its input or writing its output
-  rc = c->ctl->barrier(tmo(c));
+  rc = c->ctl->barrier(wait_limit(c));
   if (rc != XMPI_OK) {
     set_last_error("zero-copy collective: a peer did not finish");
     return rc;

@@ -1121,9 +1121,22 @@ def sc_lifecycle_stress(comm, args):
     rank, size = comm.rank(), comm.size()
     rnd = random.Random(1234 + rank)
     base = args.get("key", "life")
+    if args.get("failed_init_first"):
+        # an xmpi_init that fails half-way comes first (the test's environment: no flag pages, and the driver refuses rank 1 the mapping of
+        # rank 0's window -- once): the vote finds no transport left, every rank leaves through the failure exit holding a window, a stream
+        # and (rank 0) a mapping of its peer's window -- all of it goes back to the per-process pools, and the lifetimes below take it from there
+        try:
+            xmpi.Comm(rank, size, comm.device(), f"{base}-refused")
+        except xmpi.XmpiError as e:
+            assert "no transport left" in str(e), e
+        else:
+            raise AssertionError("xmpi_init succeeded although a window could not be mapped and there are no flag pages")
+    free_mib = comm.get_param("hbm_free_mib")
     t_start = time.time()
     for it in range(args.get("iters", 50)):
         c2 = xmpi.Comm(rank, size, comm.device(), f"{base}-{it}")
+        if args.get("failed_init_first") and it == 0:  # (its window is the one the failed attempt allocated, not another)
+            assert comm.get_param("hbm_free_mib") >= free_mib - 1 and c2.get_param("window_bytes") >= 8 << 20
         c2.set_param("copy_engine", 1)
         c2.set_param("batch_copies", 1)
         for algo in (xmpi.ALGO_RING, xmpi.ALGO_DIRECT, xmpi.ALGO_AUTO):

@@ -346,6 +346,14 @@ def test_no_transport_at_all_fails_init_on_every_rank_at_once(devsim_lib):
     assert time.time() - t0 < 40, "the ranks waited for a clock instead of each other"
 
 
+def test_an_init_that_failed_half_way_gives_back_what_it_took(devsim_lib):
+    """the same verdict for ONE attempt (the second window mapping on device 1 is refused, once; XMPI_DSYNC=0: no flag pages to fall back
+    on): xmpi_init fails on every rank, and the communicators the same processes create afterwards -- out of the windows, streams and
+    mappings the failed attempt handed back to the per-process pools -- work (tests/scenarios.py sc_lifecycle_stress)"""
+    run_ranks("lifecycle_stress", 2, {"iters": 5, "failed_init_first": 1}, timeout=300,
+              env={"XMPI_DSYNC": "0", "DEVSIM_FAIL_IPC_OPEN": "2@1", "XMPI_INIT_TIMEOUT_S": "30", "XMPI_TIMEOUT_S": "30"})
+
+
 @pytest.mark.parametrize("what", ["allreduce", "split", "ring", "ll", "recv"])
 def test_a_peer_that_dies_is_an_error_not_a_hang(devsim_lib, what):
     """the last of 3 ranks exits without a word; the survivors' next collective (one kernel / meet-body-done / ring kernel / LL

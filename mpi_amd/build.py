@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra"]
 
-LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "api.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "trace.cpp"]
+LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "p2p.cpp", "agent.cpp", "api.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "dsync_conn.cpp", "trace.cpp"]
 LIB_HEADERS = ["kernels.h", "kdev.h", "sched_steps.h", "comm.h", "ctl.h", "plan.h", "trace.h", os.path.join("..", "..", "include", "xmpi.h"),
                os.path.join("..", "..", "include", "xmpi_test.h")]
 
@@ -179,7 +179,7 @@ TSAN_HOST_SOURCES = [s for s in LIB_SOURCES if s.endswith(".cpp")]
 
 
 def build_tsan(force: bool = False) -> str:
-    """tests/tsan_host_bin: the library's host sources (every .cpp of LIB_SOURCES: api.cpp, init.cpp, pool.cpp, tune.cpp, ctl.cpp, engine.cpp, heap.cpp, ...) compiled with
+    """tests/tsan_host_bin: the library's host sources (every .cpp of LIB_SOURCES: api.cpp, init.cpp, pool.cpp, tune.cpp, ctl.cpp, engine.cpp, p2p.cpp, agent.cpp, heap.cpp, ...) compiled with
     -fsanitize=thread and driven by tests/tsan_host_driver.cpp with the ranks as threads (test infrastructure: the shared-memory
     protocols of the code that ships, raced under the sanitizer on the CPU).  The kernel objects are the library's own."""
     build_lib(False)

@@ -137,7 +137,7 @@ struct xmpi_comm {
   uint64_t* p2p_done_dev = nullptr;
   uint64_t p2p_done_next = 0;
   std::atomic<uint64_t> p2p_pull_next{0};
-  long p2p_grid_cap = 0;             // blocks of the pull kernel; 0 = from where the payload lies (engine.cpp p2p_pull_cap)
+  long p2p_grid_cap = 0;             // blocks of the pull kernel; 0 = from where the payload lies (p2p.cpp p2p_pull_cap)
   double link_gbps[xmpi::kMaxRanks] = {0};  // what xmpi_link_probe measured towards each peer (best of its calls)
   long p2p_kernel_ack = 1;           // blocking Receive: one kernel copies AND acks (0: hipMemcpyAsync / copy kernel + event + host ack)
   long p2p_agent_us = 40;            // ... by a kernel that stays this long after a message (the receive agent, sched.hip): the next
@@ -164,7 +164,7 @@ struct xmpi_comm {
   char* host_bounce_dev = nullptr;
   uint64_t host_bounce_calls = 0;
   bool lanes_dev_ok = false;  // the host lanes are pinned and mapped: kernels / DMA engines read them (ctl_dev + offset)
-  std::mutex p2p_bounce_mu;   // a message out of a peer's HBM into a host slice: through this pinned block (engine.cpp)
+  std::mutex p2p_bounce_mu;   // a message out of a peer's HBM into a host slice: through this pinned block (p2p.cpp)
   char* p2p_bounce = nullptr;
   char* p2p_bounce_dev = nullptr;
   uint32_t* p2p_tickets = nullptr;      // device: block counters of the pull kernels (blocking Receive), one per done slot
@@ -307,9 +307,11 @@ int p2p_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest, i
 int p2p_wait(xmpi_comm* c, int dest, int tag);
 int p2p_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, int tag, size_t* got_bytes);
 int p2p_probe(xmpi_comm* c, int src, int tag, size_t* bytes, int* dtype);
+// agent.cpp: the receive agent copies and acknowledges message `m` (true), or the caller launches its own kernel (false)
+bool agent_submit(xmpi_comm* c, void* dst, const void* from, size_t bytes, MailEntry* m);
 void p2p_agent_stop(xmpi_comm* c);
 // consecutive: the previous call into the library on this communicator was a collective the agent ran (its epoch + 1 is this one's)
-// 1 = done, 0 = not taken (launch instead), -1 = failed after it was taken (engine.cpp)
+// 1 = done, 0 = not taken (launch instead), -1 = failed after it was taken (agent.cpp)
 int agent_submit_ll(xmpi_comm* c, const void* send, void* recv, size_t bytes, int ll_coll, int root, int dtype, int op, bool consecutive);
 // the number of the public call this thread is in (XMPI_ENTER: the value its fetch_add of api_calls gave back, plus one)
 extern thread_local uint64_t t_api_call;
@@ -374,13 +376,14 @@ inline void pinned_words(size_t bytes, uint64_t** host, uint64_t** dev) {
 // tune.cpp
 int job_barrier(xmpi_comm* c);
 int init_selfcheck(xmpi_comm* c);
-// dsync.cpp
+// dsync_conn.cpp
 int dsync_prepare(xmpi_comm* c);
 int dsync_connect(xmpi_comm* c, double timeout_s);
 void dsync_finalize(xmpi_comm* c);
 void dsync_start_helper(xmpi_comm* c);
 void dsync_stop_helper(xmpi_comm* c);
 void dsync_service(xmpi_comm* c);
+// dsync.cpp
 bool dsync_usable(const xmpi_comm* c);
 // algo: AUTO / ZCOPY (one fold per rank: one kernel, or meet / body / done), ZPUSH, RING, RHD, TREE (the stepped kernels)
 int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,

@@ -75,7 +75,7 @@ int xmpi_ctl_selftest(const char* job_key, int rank, int size, int rounds) {
       rc = XMPI_ERR_STATE;
     out->state.store(MAIL_FREE, std::memory_order_release);
     if (rc != XMPI_OK) break;
-    // a host-resident payload through the entry's host lane (engine.cpp p2p_send / p2p_recv, DIRECT_HOST): a ring of
+    // a host-resident payload through the entry's host lane (p2p.cpp send_through_host_lane / recv_from_host_lane, DIRECT_HOST): a ring of
     // kHostLaneSlots pieces, head written by the sender, tail by the receiver; every rank sends to the next and receives from
     // the one before at once, lengths from one byte to three times the ring
     if (ctl->host_lane_bytes() > 0) {
@@ -160,7 +160,7 @@ int xmpi_ctl_selftest(const char* job_key, int rank, int size, int rounds) {
     }
     if (rc != XMPI_OK) break;
     // device-synchronised collectives: a rank publishes a registration (slot k % 4), every peer reads it and
-    // acknowledges, and the owner goes on only when all have (dsync.cpp `publish` / `dsync_service` / `await_acks`)
+    // acknowledges, and the owner goes on only when all have (dsync.cpp `publish` / `await_acks`, dsync_conn.cpp `dsync_service`)
     PubTable* pt = ctl->published(rank);
     const uint64_t n = pt->count.load(std::memory_order_relaxed);
     PubEntry& pe = pt->e[n % kPubRing];

@@ -53,7 +53,7 @@ void release_memory(xmpi_comm* c) {
   if (c->p2p_tickets) (void)hipFree(c->p2p_tickets);
   if (c->p2p_done) (void)hipHostFree(c->p2p_done);
   if (c->p2p_cmd) (void)hipHostFree(c->p2p_cmd);
-  if (c->p2p_bounce) (void)hipHostFree(c->p2p_bounce);  // (engine.cpp p2p_recv: device -> host slice through pinned memory)
+  if (c->p2p_bounce) (void)hipHostFree(c->p2p_bounce);  // (p2p.cpp recv_direct_to_host: device -> host slice through pinned memory)
   c->p2p_bounce = c->p2p_bounce_dev = nullptr;
   if (c->p2p_rec) (void)hipFree(c->p2p_rec);
   if (c->window) pool_release(c->window);  // exported memory is never given back by the runtime: the next communicator reuses it
@@ -273,7 +273,7 @@ int choose_streams(xmpi_comm* c) {
 }
 
 // the control block as the GPU sees it: kernels read the job's abort flag there and write the ack of a
-// point-to-point message straight into its mail entry (engine.cpp)
+// point-to-point message straight into its mail entry (p2p.cpp)
 // (with the host lanes behind it, so that a lane's piece is copied to a device destination by DMA; the control
 // structures alone if the runtime will not pin that much); and the words GPU and host pass each other.  None of it is fatal.
 void map_control_words(xmpi_comm* c) {

@@ -237,7 +237,7 @@ hipError_t launch_dsync_ll(const DsyncLLArgs& a, int dtype, int op, hipStream_t 
                            hipEvent_t ev_stop = nullptr);
 
 // The LL AGENT (ll.hip ll_agent_kernel): a one-block kernel that lingers behind a BLOCKING small collective and runs the next
-// one without a launch.  The host writes a 32-byte command into pinned memory (as engine.cpp agent_submit does for the receive
+// one without a launch.  The host writes a 32-byte command into pinned memory (as agent.cpp agent_submit does for the receive
 // agent, sched.hip p2p_agent_kernel):
 //   w0 = doorbell (1 = an LL collective, 2 = stop) | bytes per rank << 2 (22 bits) | seq << 24     w1 = send buffer
 //   w2 = receive buffer            w3 = collective (DsyncLLColl) | root << 2 | dtype << 6 | operation << 9 | consecutive << 11 | seq << 32

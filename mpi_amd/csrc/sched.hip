@@ -553,7 +553,7 @@ __global__ __launch_bounds__(kBlock) void p2p_recv_kernel(P2PArgs a) {
   p2p_host_done(a, s_status, s_bytes);
 }
 
-// The blocking Receive's copy (engine.cpp p2p_recv): the host has matched the message, so nothing here waits for a
+// The blocking Receive's copy (p2p.cpp p2p_recv): the host has matched the message, so nothing here waits for a
 // peer -- the payload comes straight out of the sender's buffer, and the block that finishes last writes the ack
 // where the SENDER's host thread polls (its mail entry in the shared control block, over PCIe) and the completion word
 // where this rank's host thread polls.  No event, no host hop between the copy and the ack (network.go:616-624).
@@ -577,7 +577,7 @@ __global__ __launch_bounds__(kBlock) void p2p_pull_kernel(P2PPullArgs a) {
   if (a.host_done) __hip_atomic_store(a.host_done, a.done_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// The receive AGENT (engine.cpp p2p_recv / agent_submit): the same copy-and-ack, by a kernel that STAYS for a while.
+// The receive AGENT (p2p.cpp p2p_recv / agent.cpp agent_submit): the same copy-and-ack, by a kernel that STAYS for a while.
 // A blocking Receive pays one kernel launch per message -- about 5 us before the first wave runs, most of an 8 us half
 // round trip -- and a ping-pong cannot hide it (the Receive is called when the message is already on its way).  So the
 // kernel that served a message does not end at once: block 0 goes back to watching the command record in pinned host

@@ -357,7 +357,7 @@ static void note_rejections(xmpi_comm* c, const char* who, const std::string& wh
 }
 
 // Send / Receive out of registered HBM straight into HBM -- the receiver's kernel LOADS the payload out of the sender's memory (the
-// lingering receive agent up to 512 KiB, the pull kernel above: engine.cpp p2p_recv) --: every rank sends `bytes` of its pattern to its
+// lingering receive agent up to 512 KiB, the pull kernel above: p2p.cpp p2p_recv) --: every rank sends `bytes` of its pattern to its
 // right neighbour and counts what differs in what its left one sent (even ranks send first, odd ranks receive first: the blocking
 // pair is a rendezvous, network.go:569).  Collective.
 static int p2p_check_round(xmpi_comm* c, AnswerCheck& chk, size_t bytes, uint64_t* bad) {
@@ -427,7 +427,7 @@ int init_selfcheck(xmpi_comm* c) {
   const double t_begin = now_seconds();
   t_api_call = c->api_calls.fetch_add(1, std::memory_order_relaxed) + 1;  // (as a public call: XMPI_ENTER)
   // the diagnostic counters count the CALLER's traffic (tests and benchmarks read them as such): what the check itself moves is taken out again
-  // (the receive agent's launches are NUMBERED by a counter of their own -- p2p_agent_launch_no, engine.cpp agent_submit -- which goes on counting)
+  // (the receive agent's launches are NUMBERED by a counter of their own -- p2p_agent_launch_no, agent.cpp agent_submit -- which goes on counting)
   typedef uint64_t xmpi_comm::*Counter;
   static const Counter kCounters[13] = {&xmpi_comm::p2p_direct_count, &xmpi_comm::p2p_staged_count, &xmpi_comm::p2p_lane_count, &xmpi_comm::p2p_agent_served,
                                         &xmpi_comm::p2p_agent_launches, &xmpi_comm::dsync_launches, &xmpi_comm::dsync_ll_launches, &xmpi_comm::dsync_ll_agent,

@@ -246,7 +246,7 @@ void drop_retired(xmpi_comm* c) {
 }
 }  // namespace
 
-// point-to-point rendezvous (engine.cpp): where `p` lives, for the peer to copy straight out of it
+// point-to-point rendezvous (p2p.cpp): where `p` lives, for the peer to copy straight out of it
 bool zc_export(xmpi_comm* c, const void* p, size_t need, BufRef* ref) {
   memset(ref, 0, sizeof *ref);
   Alloc al;

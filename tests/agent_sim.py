@@ -1,4 +1,4 @@
-"""A model of the receive agent (mpi_amd/csrc/sched.hip `p2p_agent_kernel`, mpi_amd/csrc/engine.cpp `agent_submit` /
+"""A model of the receive agent (mpi_amd/csrc/sched.hip `p2p_agent_kernel`, mpi_amd/csrc/agent.cpp `agent_submit` /
 `p2p_agent_stop`) that runs on the CPU.  Every actor -- the host thread of the Receives, block 0 of the agent, the
 blocks that only watch -- is a generator that yields before every access to memory somebody else can see; a seeded
 random scheduler picks who moves next, so one run is one interleaving and a few thousand seeds are a decent search.

@@ -4,7 +4,7 @@
 // kdev.h dsync_begin / dsync_end, the one-kernel fold, meet / body / done, the LL lines, the stepped ring / halving / tree
 // kernels, the stream-ordered Send / Receive kernels, the copy-and-ack kernel and the receive agent, and the host code that
 // enqueues them -- not a Python model of it ("nothing races the actual atomics").  Ranks that are threads on
-// DIFFERENT devices meet on the device exactly like processes do (dsync.cpp dsync_connect), and use each other's pointers
+// DIFFERENT devices meet on the device exactly like processes do (dsync_conn.cpp dsync_connect), and use each other's pointers
 // directly: ONE virtual address per word, which is what the sanitizer needs to see a race.
 //
 // What the reference would race here: network.go:448-497 (tagManager), :518-625 (Send / Receive + ack); the collectives

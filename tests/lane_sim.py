@@ -1,4 +1,4 @@
-"""A model of the host lanes (mpi_amd/csrc/engine.cpp p2p_send / p2p_recv, DIRECT_HOST; mpi_amd/csrc/ctl.h host_lane): a
+"""A model of the host lanes (mpi_amd/csrc/p2p.cpp p2p_send / p2p_recv, DIRECT_HOST; mpi_amd/csrc/ctl.h host_lane): a
 host-resident payload travels through a ring of S pieces in the job's shared segment.  The sender fills as many pieces as
 the ring holds BEFORE it posts the message, then one piece whenever the receiver's tail has made room; the receiver takes
 pieces as the head shows them -- with memcpy one by one (host destination), or in RUNS that a kernel pulls (device

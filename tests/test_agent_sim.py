@@ -1,4 +1,4 @@
-"""The receive agent's protocol (sched.hip p2p_agent_kernel / engine.cpp agent_submit), model-checked on the CPU under
+"""The receive agent's protocol (sched.hip p2p_agent_kernel / agent.cpp agent_submit), model-checked on the CPU under
 random interleavings -- tests/agent_sim.py.  The agent is the one kernel of the library that waits for the HOST; the
 hang it had in round 3 (a stale word of the launch before) is kept as a known-bad variant the model must catch."""
 import pytest

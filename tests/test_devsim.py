@@ -503,7 +503,7 @@ def test_the_scale_command_as_a_lone_process(devsim_lib, gpus, tmp_path):
     """`python bench.py --gpus N --steps K --warmup W` WITHOUT torch.distributed.run -- the `--gpus 1` command's shape carried to
     N GPUs: ONE process hosts all 8 ranks as threads and drives every GPU (bench.py Job.device_of: ranks spread over the visible
     devices; same-pid peers address each other's memory by pointer instead of through hipIpc, peer access enabled by xmpi_init --
-    dsync.cpp dsync_connect).  At N = 8 every rank thread has a GPU to itself: the ranks meet on the device, the library tunes
+    dsync_conn.cpp dsync_connect).  At N = 8 every rank thread has a GPU to itself: the ranks meet on the device, the library tunes
     itself, the line's roofline is the link roofline -- the same line the torchrun form gives."""
     import json
     import sys

@@ -1,4 +1,4 @@
-"""The host lanes (engine.cpp p2p_send / p2p_recv, DIRECT_HOST) under random interleavings -- tests/lane_sim.py (CPU only)."""
+"""The host lanes (p2p.cpp p2p_send / p2p_recv, DIRECT_HOST) under random interleavings -- tests/lane_sim.py (CPU only)."""
 import pytest
 
 from tests import lane_sim as sim

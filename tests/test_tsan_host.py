@@ -1,4 +1,4 @@
-"""The host side of the library -- the shared-memory protocols of ctl.cpp and engine.cpp's blocking Send / Receive of host slices --
+"""The host side of the library -- the shared-memory protocols of ctl.cpp and p2p.cpp's blocking Send / Receive of host slices --
 built with -fsanitize=thread and raced with the ranks as threads of one process (tests/tsan_host_driver.cpp).  The *_sim.py tests
 check models of the protocols; this checks the atomics of the code that ships.  No GPU involved."""
 import os

@@ -1,7 +1,7 @@
 // tsan_host_driver.cpp -- the library's REAL host-side shared-memory protocol code under ThreadSanitizer (test infrastructure).
 //
 // tests/*_sim.py check Python models of the protocols; this races the C++ that ships: ctl.cpp (join, barrier, pipe counters, mail
-// entries, descriptors, retire logs, publication table, host lanes -- through xmpi_ctl_selftest) and engine.cpp's blocking
+// entries, descriptors, retire logs, publication table, host lanes -- through xmpi_ctl_selftest) and p2p.cpp's blocking
 // Send / Receive of host slices (TagGuard, mail entries, host lanes, acks, truncation, withdrawal -- p2p_send / p2p_recv /
 // p2p_probe), with the ranks as THREADS of this process that address the control block through ONE mapping
 // (XMPI_CTL_SHARE_MAPPING=1: the sanitizer tells accesses apart by virtual address).  Built by `python -m mpi_amd.build --tsan`

@@ -23,6 +23,13 @@ type Collective interface {
 	Barrier() error
 }
 
+// Personal is implemented by backends that also provide the collectives in which every rank gives every peer a DIFFERENT
+// block (xgmi.Backend does): send holds Size() equal blocks, block j is for rank j.
+type Personal interface {
+	ReduceScatter(send, recv interface{}, op int) error
+	Alltoall(send, recv interface{}) error
+}
+
 var errNoCollectives = errors.New("mpi: the registered implementation provides no collectives")
 
 // Bcast replicates root's buffer on every rank.
@@ -53,6 +60,23 @@ func Allreduce(send, recv interface{}, op int) error {
 func Allgather(send, recv interface{}) error {
 	if c, ok := mpier.(Collective); ok {
 		return c.Allgather(send, recv)
+	}
+	return errNoCollectives
+}
+
+// ReduceScatter folds block Rank() of every rank's send buffer, in rank order, into recv (one block): the other half of Allgather.
+func ReduceScatter(send, recv interface{}, op int) error {
+	if c, ok := mpier.(Personal); ok {
+		return c.ReduceScatter(send, recv, op)
+	}
+	return errNoCollectives
+}
+
+// Alltoall delivers block j of every rank's send buffer to rank j, in rank order, into recv: the exchange
+// examples/helloworld/helloworld.go:53-81 performs with one Send / Receive pair per peer, as one call.
+func Alltoall(send, recv interface{}) error {
+	if c, ok := mpier.(Personal); ok {
+		return c.Alltoall(send, recv)
 	}
 	return errNoCollectives
 }

@@ -348,6 +348,38 @@ func (b *Backend) Allgather(send, recv interface{}) error {
 	return status(C.xmpi_allgather(b.comm, sp, rp, C.size_t(n), C.xmpi_dtype(dt), 0), "mpi allgather")
 }
 
+var errBlocks = errors.New("xgmi: the send buffer does not hold one block per rank")
+
+// ReduceScatter folds block Rank() of the ranks' send buffers (Size() equal blocks each), in rank order, into recv (one block).
+// Out of place.  (mpi.Personal of go/mpi_collectives/collectives.go.)
+func (b *Backend) ReduceScatter(send, recv interface{}, op int) error {
+	sp, n, dt, ok1 := view(send)
+	rp, _, _, ok2 := view(recv)
+	if !ok1 || !ok2 {
+		return errPayload
+	}
+	size := b.Size()
+	if size < 1 || n%size != 0 {
+		return errBlocks
+	}
+	return status(C.xmpi_reduce_scatter(b.comm, sp, rp, C.size_t(n/size), C.xmpi_dtype(dt), C.xmpi_op(op), 0), "mpi reduce_scatter")
+}
+
+// Alltoall delivers block j of this rank's send buffer to rank j; recv holds the ranks' blocks for this rank in rank order -- the
+// exchange of the reference's helloworld (helloworld.go:53-81) as one call.  Out of place.
+func (b *Backend) Alltoall(send, recv interface{}) error {
+	sp, n, dt, ok1 := view(send)
+	rp, _, _, ok2 := view(recv)
+	if !ok1 || !ok2 {
+		return errPayload
+	}
+	size := b.Size()
+	if size < 1 || n%size != 0 {
+		return errBlocks
+	}
+	return status(C.xmpi_alltoall(b.comm, sp, rp, C.size_t(n/size), C.xmpi_dtype(dt), 0), "mpi alltoall")
+}
+
 // Barrier is a host-side rendezvous of all ranks.
 func (b *Backend) Barrier() error { return status(C.xmpi_barrier(b.comm), "mpi barrier") }
 
@@ -410,6 +442,15 @@ func (b *Backend) AllreduceOnStream(send, recv DeviceBuffer, op int, stream unsa
 func (b *Backend) AllgatherOnStream(send, recv DeviceBuffer, stream unsafe.Pointer) error {
 	return status(C.xmpi_allgather_on_stream(b.comm, send.Ptr, recv.Ptr, C.size_t(send.Count), C.xmpi_dtype(send.Type),
 		stream), "mpi allgather")
+}
+// reduce-scatter: recv.Count = elements per block (send holds Size() of them); all-to-all: blockCount
+func (b *Backend) ReduceScatterOnStream(send, recv DeviceBuffer, op int, stream unsafe.Pointer) error {
+	return status(C.xmpi_reduce_scatter_on_stream(b.comm, send.Ptr, recv.Ptr, C.size_t(recv.Count), C.xmpi_dtype(send.Type),
+		C.xmpi_op(op), stream), "mpi reduce_scatter")
+}
+func (b *Backend) AlltoallOnStream(send, recv DeviceBuffer, blockCount int, stream unsafe.Pointer) error {
+	return status(C.xmpi_alltoall_on_stream(b.comm, send.Ptr, recv.Ptr, C.size_t(blockCount), C.xmpi_dtype(send.Type),
+		stream), "mpi alltoall")
 }
 func (b *Backend) BcastOnStream(buf DeviceBuffer, root int, stream unsafe.Pointer) error {
 	return status(C.xmpi_bcast_on_stream(b.comm, buf.Ptr, C.size_t(buf.Count), C.xmpi_dtype(buf.Type), C.int(root), stream), "mpi bcast")

@@ -328,6 +328,33 @@ int xmpi_allreduce_repeat(xmpi_comm* comm, const void* sendbuf, void* recvbuf, s
 int xmpi_allgather(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
                    xmpi_dtype dtype, int algo);
 
+/* (absent from the reference, mpi.go:130)  The other half of xmpi_allgather: recvbuf[0 : count] = op over ranks r, in rank order
+ * 0..N-1, of rank r's sendbuf[me*count : (me+1)*count] -- what sharded optimisers pair with the allgather, instead of a whole
+ * allreduce of which (N-1)/N is thrown away.  count = elements per BLOCK: sendbuf holds size*count, recvbuf count.  Out of place
+ * only (the buffers overlap: XMPI_ERR_ARG).  algo: ZCOPY | ZPUSH | LL | DIRECT | AUTO (anything else: XMPI_ERR_UNSUPPORTED); every
+ * one of them gives the same bits.  One process per GPU: one kernel folds block `me` straight out of the peers' send buffers (ZCOPY),
+ * or every rank stores its blocks into the peers' landing blocks and folds locally (ZPUSH: nothing is read over a link), or --
+ * blocks up to 32 KiB, what AUTO does up to ll_bytes per block -- the blocks travel as {data, flag} lines (LL).  Blocks whose
+ * length is a multiple of 16 bytes move as 16-byte packets; others one element at a time (correct, slow).  Ranks that meet on the
+ * host: one fold kernel, or (DIRECT, unregistered buffers) a step table through the windows.  Not known to xmpi_tune. */
+int xmpi_reduce_scatter(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
+                        xmpi_dtype dtype, xmpi_op op, int algo);
+
+/* (absent from the reference, mpi.go:130; it is the one exchange the reference's own program performs, helloworld.go:53-81: a
+ * distinct message from every rank to every rank, there as N-1 Send / Receive pairs per rank)
+ * recvbuf[r*count : (r+1)*count] = rank r's sendbuf[me*count : (me+1)*count], bit-exact.  count = elements per block: both buffers
+ * hold size*count.  Out of place only.  algo: ZCOPY | LL | DIRECT | AUTO.  One process per GPU: every rank STORES its block j into
+ * rank j's receive buffer (one kernel, a segment per destination), or -- blocks up to 32 KiB -- pushes them as LL lines. */
+int xmpi_alltoall(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
+                  xmpi_dtype dtype, int algo);
+
+/* (absent from the reference, mpi.go:130; the all-to-all is helloworld.go:53-81's exchange)  The stream-ordered forms of the two,
+ * with AUTO's schedule, under the rules of xmpi_allreduce_on_stream above. */
+int xmpi_reduce_scatter_on_stream(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
+                                  xmpi_dtype dtype, xmpi_op op, void* stream);
+int xmpi_alltoall_on_stream(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
+                            xmpi_dtype dtype, void* stream);
+
 /* ---- local kernels (the HBM-bound pieces, exposed for parity tests and rooflines) --------- */
 
 /* (No counterpart in the reference: a reference user adds on the host what Receive delivered, the helloworld.go:53-81 idiom.)

@@ -132,7 +132,8 @@ def build_host(force: bool = False) -> list[str]:
                           ("coll_sweep", os.path.join(ROOT, "examples", "coll_sweep.cpp")),
                           ("allreduce_bench", os.path.join(ROOT, "examples", "allreduce_bench.cpp")),
                           ("cfg5_sweep", os.path.join(ROOT, "examples", "cfg5_sweep.cpp")),
-                          ("cfg3_allgather", os.path.join(ROOT, "examples", "cfg3_allgather.cpp"))):
+                          ("cfg3_allgather", os.path.join(ROOT, "examples", "cfg3_allgather.cpp")),
+                          ("alltoall", os.path.join(ROOT, "examples", "alltoall.cpp"))):
             if os.path.exists(src):
                 out = os.path.join(BIN, name)
                 if force or _newer(out, [src] + deps):

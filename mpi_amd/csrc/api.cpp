@@ -163,8 +163,7 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
 
   // host-resident buffers: stage through this rank's HBM (convenience path; the hot path is HBM)
   const bool send_dev = is_device_pointer(sendbuf), recv_dev = is_device_pointer(recvbuf);
-  const size_t send_bytes = total;
-  const size_t recv_bytes = (coll == COLL_ALLGATHER) ? total * (size_t)c->size : total;
+  const size_t send_bytes = coll_send_bytes(coll, c->size, total), recv_bytes = coll_recv_bytes(coll, c->size, total);
   void *dsend = const_cast<void*>(sendbuf), *drecv = recvbuf;
   void *tmp_send = nullptr, *tmp_recv = nullptr;
   if (!recv_dev) {
@@ -173,7 +172,7 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
     if (coll == COLL_BCAST) XMPI_HIP(hipMemcpy(tmp_recv, recvbuf, recv_bytes, hipMemcpyHostToDevice));
   }
   if (!send_dev) {
-    if (sendbuf == recvbuf && coll != COLL_ALLGATHER) {
+    if (sendbuf == recvbuf && coll != COLL_ALLGATHER && !coll_personal(coll)) {
       if (coll != COLL_BCAST) XMPI_HIP(hipMemcpy(drecv, sendbuf, send_bytes, hipMemcpyHostToDevice));
       dsend = drecv;
     } else {
@@ -192,6 +191,25 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
   return rc;
 }
 
+// reduce-scatter: ZCOPY | ZPUSH | LL | DIRECT | AUTO; all-to-all: ZCOPY | LL | DIRECT | AUTO
+static bool personal_algo_ok(int coll, int algo) {
+  const bool ok = algo == XMPI_ALGO_AUTO || algo == XMPI_ALGO_ZCOPY || algo == XMPI_ALGO_LL || algo == XMPI_ALGO_DIRECT ||
+                  (algo == XMPI_ALGO_ZPUSH && coll == COLL_REDUCE_SCATTER);
+  if (!ok) set_last_error(std::string(coll_name(coll)) + " has no " + algo_name(algo) + " schedule (" +
+                          (coll == COLL_REDUCE_SCATTER ? "zcopy | zpush | ll | direct | auto" : "zcopy | ll | direct | auto") + ")");
+  return ok;
+}
+
+// reduce-scatter and all-to-all are out of place: a rank's receive buffer is written while peers (and its own later blocks) still
+// read its send buffer
+static bool personal_overlap(const xmpi_comm* c, int coll, const void* sendbuf, const void* recvbuf, size_t unit) {
+  const uintptr_t s = (uintptr_t)sendbuf, r = (uintptr_t)recvbuf;
+  const size_t sb = coll_send_bytes(coll, c->size, unit), rb = coll_recv_bytes(coll, c->size, unit);
+  if (s >= r + rb || r >= s + sb) return false;
+  set_last_error(std::string(coll_name(coll)) + " is out of place only: the send and the receive buffer overlap");
+  return true;
+}
+
 static int collective(xmpi_comm* c, int coll, int algo, int root, const void* sendbuf, void* recvbuf, size_t count,
                       int dtype, int op) {
   drain_worker(c);
@@ -200,11 +218,14 @@ static int collective(xmpi_comm* c, int coll, int algo, int root, const void* se
     set_last_error("bad dtype / op / root / algo");
     return XMPI_ERR_ARG;
   }
+  // reduce-scatter and all-to-all: the schedules that exist for them, decided from the arguments alone (every rank answers alike)
+  if (coll_personal(coll) && !personal_algo_ok(coll, algo)) return XMPI_ERR_UNSUPPORTED;
   if (count == 0) return XMPI_OK;
   if (!recvbuf || !sendbuf) {
     set_last_error("null buffer");
     return XMPI_ERR_ARG;
   }
+  if (coll_personal(coll) && personal_overlap(c, coll, sendbuf, recvbuf, count * es)) return XMPI_ERR_ARG;
   RoctxRange range("xmpi:%s algo=%s bytes=%zu rank=%d/%d", coll_name(coll), algo_name(algo), count * es, c->rank, c->size);
   std::lock_guard<std::mutex> g(c->coll_mu);
   // One process per GPU (the production layout): the ranks meet on the device (dsync.cpp) -- one kernel per
@@ -221,7 +242,7 @@ static int collective(xmpi_comm* c, int coll, int algo, int root, const void* se
   // one copy down on the communicator's stream.  No arena memory left: the staged path's own temporary buffers (below).
   const bool send_host = !is_device_pointer(sendbuf), recv_host = !is_device_pointer(recvbuf);
   if (send_host || recv_host) {
-    const size_t send_bytes = count * es, recv_bytes = coll == COLL_ALLGATHER ? send_bytes * (size_t)c->size : send_bytes;
+    const size_t send_bytes = coll_send_bytes(coll, c->size, count * es), recv_bytes = coll_recv_bytes(coll, c->size, count * es);
     const bool in_place = sendbuf == recvbuf && coll != COLL_ALLGATHER;
     void* up_recv = recv_host ? heap_alloc(c->device, recv_bytes) : nullptr;
     void* up_send = send_host && !(in_place && recv_host) ? heap_alloc(c->device, send_bytes) : nullptr;
@@ -474,6 +495,16 @@ int xmpi_allgather(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t coun
   return collective(c, COLL_ALLGATHER, algo, 0, sendbuf, recvbuf, count, (int)dtype, XMPI_SUM);
 }
 
+int xmpi_reduce_scatter(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, xmpi_op op, int algo) {
+  XMPI_ENTER(c);
+  return collective(c, COLL_REDUCE_SCATTER, algo, 0, sendbuf, recvbuf, count, (int)dtype, (int)op);
+}
+
+int xmpi_alltoall(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, int algo) {
+  XMPI_ENTER(c);
+  return collective(c, COLL_ALLTOALL, algo, 0, sendbuf, recvbuf, count, (int)dtype, XMPI_SUM);
+}
+
 // ---- stream-ordered forms --------------------------------------------------------------------------
 static int on_stream(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype, int op,
                      void* stream) {
@@ -487,12 +518,13 @@ static int on_stream(xmpi_comm* c, int coll, int root, const void* sendbuf, void
     set_last_error("null buffer");
     return XMPI_ERR_ARG;
   }
+  if (coll_personal(coll) && personal_overlap(c, coll, sendbuf, recvbuf, count * es)) return XMPI_ERR_ARG;
   drain_worker(c);
   std::lock_guard<std::mutex> g(c->coll_mu);
   hipStream_t s = stream ? (hipStream_t)stream : c->local_stream;
   if (c->size == 1) {  // a job of one: the result is the input
     if (coll != COLL_BCAST && sendbuf != recvbuf) XMPI_HIP(hipMemcpyAsync(recvbuf, sendbuf, count * es, hipMemcpyDefault, s));
-    return XMPI_OK;
+    return XMPI_OK;  // (reduce-scatter, all-to-all: one block of `count` elements too)
   }
   if (!dsync_usable(c)) {
     // ranks sharing a (process, GPU) pair meet on the host (see dsync.cpp): order the call after the stream's
@@ -538,6 +570,17 @@ int xmpi_reduce_on_stream(xmpi_comm* c, const void* sendbuf, void* recvbuf, size
     return XMPI_ERR_ARG;
   }
   return on_stream(c, COLL_REDUCE, root, sendbuf, rb, count, (int)dtype, (int)op, stream);
+}
+
+int xmpi_reduce_scatter_on_stream(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, xmpi_op op,
+                                  void* stream) {
+  XMPI_ENTER(c);
+  return on_stream(c, COLL_REDUCE_SCATTER, 0, sendbuf, recvbuf, count, (int)dtype, (int)op, stream);
+}
+
+int xmpi_alltoall_on_stream(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, void* stream) {
+  XMPI_ENTER(c);
+  return on_stream(c, COLL_ALLTOALL, 0, sendbuf, recvbuf, count, (int)dtype, XMPI_SUM, stream);
 }
 
 void* xmpi_stream_create(xmpi_comm* c) {

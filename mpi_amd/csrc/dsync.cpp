@@ -20,6 +20,11 @@
 // Ranks hosted by threads of one process on one GPU (bench.py on a single-GPU box) keep the host-synchronised
 // path: they share one in-order stream, and a kernel that waits for a kernel queued behind it never ends.
 //
+// Six collectives are segment lists over the same kernels (DsyncSeg: whose buffers a block reads, whose it writes).  Reduce-scatter and
+// all-to-all cut their buffers into BLOCKS of count elements, which -- unlike the 16-byte aligned chunks the others are cut into
+// (zc_chunk) -- start wherever me x count x element size falls: blocks that are a multiple of 16 bytes take the fold kernel's
+// packet path, any other length its one-element-per-lane path (correct, slow).
+//
 // The connection lifecycle (dsync_prepare / dsync_connect / the helper thread / dsync_finalize) and dsync_service: dsync_conn.cpp.
 #include <time.h>
 #include <unistd.h>
@@ -186,8 +191,9 @@ struct Resolved {
 // a collective's arguments, as its steps read them
 struct CollArgs {
   int coll, root, dtype, op;
-  size_t count, es;               // elements per rank, bytes per element
-  size_t send_bytes, recv_bytes;  // per rank; allgather's receive buffer holds N blocks
+  size_t count, es;               // elements per rank (reduce-scatter, all-to-all: per block), bytes per element
+  size_t unit;                    // count x es: the message, or -- reduce-scatter, all-to-all -- the block one rank gives one peer
+  size_t send_bytes, recv_bytes;  // what the buffers hold (plan.h coll_send_bytes / coll_recv_bytes)
 };
 
 // pinned memory for the host slices of blocking collectives; false = not available (the runtime's own staged copies serve)
@@ -415,7 +421,7 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   const hipStream_t stream = call.stream;
   const bool blocking = call.blocking;
   const int N = c->size, me = c->rank, coll = k.coll, root = k.root;
-  const size_t unit = k.send_bytes, recv_bytes = k.recv_bytes;
+  const size_t unit = k.unit, send_bytes = k.send_bytes, recv_bytes = k.recv_bytes;
   RoctxRange range("xmpi:dsync %s form=ll bytes=%zu epoch=%llu %s", coll_name(coll), unit, (unsigned long long)c->dsync_epoch + 1,
                    blocking ? "blocking" : "enqueued");
   const bool reads = coll != COLL_BCAST || me == root;           // this rank's send buffer is read
@@ -427,20 +433,20 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   const void* send = sendbuf;
   void* recv = recvbuf;
   // a host slice: through pinned memory the kernel reads / writes itself, or a stand-in
-  const bool host_in = reads && !on_gpu(sendbuf, unit), host_res = writes && !on_gpu(recvbuf, recv_bytes);
+  const bool host_in = reads && !on_gpu(sendbuf, send_bytes), host_res = writes && !on_gpu(recvbuf, recv_bytes);
   if (capturing && (host_in || host_res)) {
     set_last_error("graph capture needs device buffers");
     return XMPI_ERR_ARG;
   }
   if (host_in) {
-    if (blocking && host_bounce_ready(c)) {
-      memcpy(c->host_bounce, sendbuf, unit);
+    if (blocking && send_bytes <= xmpi_comm::kHostBounce && host_bounce_ready(c)) {
+      memcpy(c->host_bounce, sendbuf, send_bytes);
       send = c->host_bounce_dev;
       c->host_bounce_calls++;
     } else {
-      void* tmp = call.lend(unit);
+      void* tmp = call.lend(send_bytes);
       if (!tmp) return call.fail(XMPI_ERR_NOMEM);
-      const hipError_t ce = hipMemcpyAsync(tmp, sendbuf, unit, hipMemcpyDefault, stream);
+      const hipError_t ce = hipMemcpyAsync(tmp, sendbuf, send_bytes, hipMemcpyDefault, stream);
       if (ce != hipSuccess) return call.fail(hip_fail(ce, "hipMemcpyAsync(stand-in)", __FILE__, __LINE__));
       send = tmp;
     }
@@ -458,7 +464,8 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   }
   if (!writes) recv = const_cast<void*>(send);  // (never written; the launcher wants a pointer)
   if (!reads) send = recv;
-  const int ll_coll = coll == COLL_ALLREDUCE ? LL_ALLREDUCE : coll == COLL_REDUCE ? LL_REDUCE : coll == COLL_BCAST ? LL_BCAST : LL_ALLGATHER;
+  const int ll_coll = coll == COLL_ALLREDUCE ? LL_ALLREDUCE : coll == COLL_REDUCE ? LL_REDUCE : coll == COLL_BCAST ? LL_BCAST
+                      : coll == COLL_ALLGATHER ? LL_ALLGATHER : coll == COLL_REDUCE_SCATTER ? LL_REDUCE_SCATTER : LL_ALLTOALL;
   // A blocking call -- the only kind the reference's API has (mpi.go:47-48) -- is launch + kernel + completion word, and the
   // launch is half of it.  The LL agent (ll.hip ll_agent_kernel: a one-block kernel that lingers behind the previous blocking small
   // collective, as the receive agent does behind a Receive) runs the same lines without one: the command goes through pinned
@@ -475,7 +482,8 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   // 2 processes; host slices 10.0 against 13.8; at 16 KiB it is a tie, 12.1 / 11.7, and beyond the launched kernel's many blocks
   // win) -- scripts/r04_agent_limit.sh
   const size_t agent_limit = (size_t)std::max<long>(0, c->agent_ll_bytes);
-  if (blocking && !capturing && call.lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
+  // (the agent knows the four collectives whose ranks all send the same line; reduce-scatter and all-to-all are launched)
+  if (blocking && !capturing && !coll_personal(coll) && call.lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
       (quiet ||
        (idle(stream) && (!c->dsync_last_stream || c->dsync_last_stream == stream || idle(c->dsync_last_stream))))) {
     ++c->dsync_epoch;
@@ -536,7 +544,7 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   c->dsync_launches++;
   c->dsync_ll_launches++;
   if (!capturing) c->dsync_last_stream = stream;
-  call.traffic = 2 * unit * (size_t)N;  // (own payload read, N-1 pushes of twice its size ... : a latency path, not a bandwidth one)
+  call.traffic = 2 * unit * (size_t)N;  // (own payload read -- reduce-scatter, all-to-all: a block per peer --, N-1 pushes of twice its size ... : a latency path, not a bandwidth one)
   call.keep_prof();
   return blocking ? call.wait_and_finish(recvbuf, recv_bytes) : call.enqueued(recvbuf, recv_bytes);
 }
@@ -613,29 +621,30 @@ struct DsyncRoute {
 
 // From the communicator and the arguments only -- the same answer on every rank, so every rank refuses alike, hands the same calls
 // to LL and launches the same form.  Pure: no HIP, no counters, no error text.
-DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t send_bytes, bool capturing) {
+// unit: the message -- reduce-scatter, all-to-all: the BLOCK, which is what a slot of LL lines has to hold and what every link carries
+DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool capturing) {
   DsyncRoute rt;
   rt.unroll = (int)std::max<long>(1, std::min<long>(2, c->dsync_unroll));
   // the schedule: what the caller named, or the library's own table (xmpi_tune fills it; untuned: the zero-copy fold, split by size)
   if (algo == XMPI_ALGO_AUTO) {
     int cls = 0;
-    while (cls + 1 < xmpi_comm::kTuneClasses && (send_bytes >> (cls + 9)) != 0) cls++;
-    if (c->tuned && coll >= 0 && coll < 4) {
+    while (cls + 1 < xmpi_comm::kTuneClasses && (unit >> (cls + 9)) != 0) cls++;
+    if (c->tuned && coll >= 0 && coll < kTunedColls) {
       if (c->tune_algo[coll][cls] >= 0) algo = c->tune_algo[coll][cls];
       if (c->tune_split[coll][cls] >= 0) rt.split_pref = c->tune_split[coll][cls];
       if (c->tune_unroll[coll][cls] > 0) rt.unroll = c->tune_unroll[coll][cls];
     }
     // untuned: short messages go as {data, flag} lines (ll.hip) -- one one-way hop instead of two round trips
-    if (algo == XMPI_ALGO_AUTO && c->zero_copy && send_bytes <= (size_t)std::max<long>(0, c->ll_bytes)) algo = XMPI_ALGO_LL;
+    if (algo == XMPI_ALGO_AUTO && c->zero_copy && unit <= (size_t)std::max<long>(0, c->ll_bytes)) algo = XMPI_ALGO_LL;
   }
   // A schedule whose ANSWERS xmpi_tune or xmpi_init's self-check found wrong on this machine (tune_rejected: the outcome of a vote,
   // the same bits on every rank) is not run for a caller: AUTO never leads here (the table leaves it out, apply_rejections the untuned
   // rules), so this is a caller -- or a table written by hand -- naming it.  Every rank refuses alike, before anything is lent,
   // announced or moved.
-  const uint32_t rejected = (c->tune_running || coll < 0 || coll >= 4) ? 0u : c->tune_rejected[coll];
+  const uint32_t rejected = (c->tune_running || coll < 0 || coll >= kTunedColls) ? 0u : c->tune_rejected[coll];
   auto no = [rejected](int cand) { return ((rejected >> cand) & 1u) != 0; };
   if (algo == XMPI_ALGO_LL) {
-    if (send_bytes <= kLLMaxPayload) {
+    if (unit <= kLLMaxPayload) {
       rt.form = DsyncRoute::LL;
       rt.algo = algo;
       if (no(xmpi_comm::CAND_LL)) rt.refused = xmpi_comm::CAND_LL;
@@ -665,7 +674,7 @@ DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t send_bytes
                      : s == XMPI_ALGO_RHD ? (rt.sched_push ? xmpi_comm::CAND_RHD_PUSH : xmpi_comm::CAND_RHD)
                                           : (rt.sched_push ? xmpi_comm::CAND_TREE_PUSH : xmpi_comm::CAND_TREE);
     if (no(cand)) rt.refused = cand;
-  } else if (algo == XMPI_ALGO_ZPUSH && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE) && !capturing) {
+  } else if (algo == XMPI_ALGO_ZPUSH && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE || coll == COLL_REDUCE_SCATTER) && !capturing) {
     // (under capture the push-only form is the fold: its staging area is a block the communicator may replace later)
     rt.form = DsyncRoute::PUSH_ONLY;
     if (no(xmpi_comm::CAND_ZPUSH)) rt.refused = xmpi_comm::CAND_ZPUSH;
@@ -701,7 +710,7 @@ bool bcast_forwards(const xmpi_comm* c, size_t bytes) { return c->size > 2 && by
 // same schedule, over the same bytes end with an error before any of them has touched another's memory -- instead of a hang, or
 // of a fold over buffers of different lengths.  (One kernel or meet / body / done is NOT part of it: those mix.)
 uint64_t call_sig(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt) {
-  const bool reduces = k.coll == COLL_ALLREDUCE || k.coll == COLL_REDUCE, rooted = k.coll == COLL_BCAST || k.coll == COLL_REDUCE;
+  const bool reduces = coll_reduces(k.coll), rooted = k.coll == COLL_BCAST || k.coll == COLL_REDUCE;
   const uint64_t form = rt.form == DsyncRoute::STEPPED ? 16u + 2u * (uint64_t)rt.sched_algo + (rt.sched_push ? 1u : 0u)
                         : rt.form == DsyncRoute::PUSH_ONLY ? 2u
                         : (k.coll == COLL_BCAST && bcast_forwards(c, k.send_bytes)) ? 3u : 1u;
@@ -764,6 +773,76 @@ FoldPlan plan_allgather(const xmpi_comm* c, const CollArgs& k, int split_pref) {
   s.packets = k.send_bytes / 16;
   s.moved = (size_t)(1 + c->size) * k.send_bytes;
   s.split_pref = split_pref;
+  return p;
+}
+
+// reduce-scatter: the allreduce's fold with one local destination -- every rank folds block `me` of everybody's send buffer, in rank
+// order, into its own receive buffer.  Block `me` starts at me x B, which unlike a zc_chunk cut need not be 16-byte aligned:
+// blocks that are a multiple of 16 bytes take the kernel's packet path, others its one-element-per-lane path (correct, slow).
+FoldPlan plan_reduce_scatter(const xmpi_comm* c, const CollArgs& k, int split_pref) {
+  const int N = c->size;
+  FoldPlan p;
+  FoldStep& s = p.k[0];
+  s.nseg = 1;
+  s.seg[0].src_off = (size_t)c->rank * k.unit;
+  s.seg[0].dst_off = 0;
+  s.seg[0].count = k.count;
+  s.seg[0].src_mask = everyone(N);
+  s.seg[0].dst_mask = 1u << c->rank;
+  s.nsrc = N;
+  s.dtype = k.dtype;
+  s.op = k.op;
+  s.packets = k.count / std::max<size_t>(1, 16 / k.es);
+  s.moved = (size_t)(N + 1) * k.unit;
+  s.split_pref = split_pref;
+  return p;
+}
+
+// all-to-all, push form: one segment per destination j -- my block j into place `me` of rank j's receive buffer (the own block
+// is a segment like the others).  Every payload byte crosses its link as a posted store; N <= kDsyncRanks segments fit.
+FoldPlan plan_alltoall(const xmpi_comm* c, const CollArgs& k, int split_pref) {
+  const int N = c->size, me = c->rank;
+  FoldPlan p;
+  FoldStep& s = p.k[0];
+  for (int d = 0; d < N; d++) {  // (own block first, then the next rank's: the ranks do not all store into rank 0 first)
+    const int j = (me + d) % N;
+    DsyncSeg& g = s.seg[s.nseg++];
+    g.src_off = (size_t)j * k.unit;
+    g.dst_off = (size_t)me * k.unit;
+    g.count = k.unit;
+    g.src_mask = 1u << me;
+    g.dst_mask = 1u << j;
+  }
+  s.packets = k.unit / 16;
+  s.moved = 2 * (size_t)N * k.unit;
+  s.split_pref = split_pref;
+  return p;
+}
+
+// reduce-scatter, push-only (XMPI_ALGO_ZPUSH): plan_push_only below with blocks for zc_chunk's cuts -- my block q into region `me`
+// of rank q's landing block, then a local fold in rank order into the receive buffer.
+FoldPlan plan_reduce_scatter_push(const xmpi_comm* c, const CollArgs& k) {
+  const int N = c->size, me = c->rank;
+  const size_t region = (k.unit + 255) / 256 * 256;
+  FoldPlan p;
+  p.kernels = 2;
+  p.land = region * (size_t)N;
+  FoldStep& s = p.k[0];
+  for (int d = 1; d < N; d++) {
+    const int q = (me + d) % N;
+    DsyncSeg& g = s.seg[s.nseg++];
+    g.src_off = (size_t)q * k.unit;
+    g.dst_off = (size_t)me * region;
+    g.count = k.unit;
+    g.src_mask = 1u << me;
+    g.dst_mask = 1u << q;
+    g.dst_to_land = 1;
+  }
+  s.packets = k.unit / 16;
+  s.moved = 2 * (size_t)(N - 1) * k.unit;
+  p.k[1] = plan_reduce_scatter(c, k, -1).k[0];
+  p.k[1].seg[0].src_from_recv = 2;
+  p.k[1].seg[0].stage_stride = region;
   return p;
 }
 
@@ -1088,7 +1167,7 @@ DsyncArgs meet_args(const xmpi_comm* c, const Resolved& r, int sslot, int rslot)
 int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,
                      int op, hipStream_t stream, bool blocking, int algo) {
   const size_t es = xmpi_dtype_size((xmpi_dtype)dtype);
-  const CollArgs k{coll, root, dtype, op, count, es, count * es, count * es * (coll == COLL_ALLGATHER ? (size_t)c->size : 1)};
+  const CollArgs k{coll, root, dtype, op, count, es, count * es, coll_send_bytes(coll, c->size, count * es), coll_recv_bytes(coll, c->size, count * es)};
   if (!stream) stream = c->local_stream;
   DsyncCall call(c, stream, blocking);
   dsync_service(c);
@@ -1099,7 +1178,7 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   const bool capturing = cap != hipStreamCaptureStatusNone;
 
   // route: a refused call and an LL call end here
-  const DsyncRoute rt = dsync_route(c, coll, algo, k.send_bytes, capturing);
+  const DsyncRoute rt = dsync_route(c, coll, algo, k.unit, capturing);
   if (rt.refused >= 0) return refuse(coll, rt.refused);
   if (rt.form == DsyncRoute::LL) return dsync_ll(call, k, sendbuf, recvbuf, capturing);
   RoctxRange range("xmpi:dsync %s algo=%s bytes=%zu epoch=%llu %s", coll_name(coll), algo_name(rt.algo), k.send_bytes,
@@ -1130,7 +1209,9 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
     if (land) rc = announce_land(call, land, capturing, &sa.d);
     if (rc == XMPI_OK) rc = launch_sched(call, sa, gx, dtype, op);
   } else {
-    const FoldPlan p = rt.form == DsyncRoute::PUSH_ONLY        ? plan_push_only(c, k)
+    const FoldPlan p = rt.form == DsyncRoute::PUSH_ONLY        ? (coll == COLL_REDUCE_SCATTER ? plan_reduce_scatter_push(c, k) : plan_push_only(c, k))
+                       : coll == COLL_REDUCE_SCATTER           ? plan_reduce_scatter(c, k, rt.split_pref)
+                       : coll == COLL_ALLTOALL                 ? plan_alltoall(c, k, rt.split_pref)
                        : coll == COLL_ALLGATHER                ? plan_allgather(c, k, rt.split_pref)
                        : coll != COLL_BCAST                    ? plan_fold(c, k, rt.split_pref)
                        : bcast_forwards(c, k.send_bytes)       ? plan_bcast_forward(c, k)

@@ -166,6 +166,11 @@ static_assert(kGoOff + sizeof(P2PGo) * kP2PGoSlots <= kLLHereOff, "flag allocati
 // has finished reading epoch e-2: X has finished epoch e-1, EVERY device-synchronised collective completes on a rank only
 // after every peer has started it (the LL forms: a line or a `here` word from everybody; the others: dsync_begin), and Y
 // started e-1 after it finished e-2 (the kernels of one rank run one at a time).  tests/ll_sim.py checks exactly this.
+// The personalised forms (LL_REDUCE_SCATTER, LL_ALLTOALL: rank X's line idx in rank Y's slot is line idx of X's block Y, not of one
+// payload everybody gets) change what a line holds, not who writes where or when: a call has count > 0, so every rank still sends
+// at least one line to EVERY peer and collects one from every peer before it completes -- "a rank completes only after every peer
+// has started" holds by the data alone, without the `here` words.  A slot holds one source's payload, and each source sends this
+// rank exactly one block: the limit is kLLMaxPayload per BLOCK.
 constexpr size_t kLLOff = 1u << 20;
 constexpr size_t kLLSlotBytes = 64u << 10;          // lines of one (source rank, parity)
 constexpr size_t kLLMaxPayload = kLLSlotBytes / 2;  // 32 KiB per rank
@@ -217,7 +222,8 @@ struct DsyncArgs {
   DsyncSeg seg[kDsyncRanks];
 };
 
-enum DsyncLLColl : int32_t { LL_ALLREDUCE = 0, LL_REDUCE = 1, LL_BCAST = 2, LL_ALLGATHER = 3 };
+// (0..3 are what an agent command names in two bits; the personalised forms are launched only)
+enum DsyncLLColl : int32_t { LL_ALLREDUCE = 0, LL_REDUCE = 1, LL_BCAST = 2, LL_ALLGATHER = 3, LL_REDUCE_SCATTER = 4, LL_ALLTOALL = 5 };
 struct DsyncLLArgs {
   DsyncPage* page[kDsyncRanks];  // [me]: own flag allocation, others: the peers' as mapped here
   int32_t me, n;
@@ -228,7 +234,8 @@ struct DsyncLLArgs {
   uint64_t done_value;
   const void* send;              // this rank's buffers: any memory its own GPU can address
   void* recv;
-  uint64_t bytes;                // payload per rank (allgather: one rank's block), <= kLLMaxPayload
+  uint64_t bytes;                // payload per rank (allgather: one rank's block; reduce-scatter, all-to-all: the block one rank gives
+                                 // one peer -- the send buffer holds n of them), <= kLLMaxPayload
   const int32_t* abort_word;
   uint32_t* status;
   uint64_t spin_limit;

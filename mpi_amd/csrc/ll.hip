@@ -286,6 +286,51 @@ __device__ __forceinline__ void ll_copy_collect(const DsyncLLArgs& a, const LLCa
   }
 }
 
+// The PERSONALISED forms (reduce-scatter, all-to-all): lane idx owns line idx of EVERY block -- what it pushes to rank p is line idx
+// of its block p, not of one payload everybody gets.  Blocks start at multiples of the block length, which need not be 8-byte
+// aligned: load8 / store8 take their byte paths then (a line still holds whole elements: 8 idx and the block length are multiples
+// of the element size).
+__device__ __forceinline__ void ll_personal_push(const DsyncLLArgs& a, const LLCall& q, uint32_t parity, uint32_t flag, size_t idx) {
+  const int me = a.me, n = a.n;
+  const uint32_t valid = q.bytes - idx * 8 >= 8 ? 8u : (uint32_t)(q.bytes - idx * 8);
+  const char* send = reinterpret_cast<const char*>(q.send);
+  uint64_t x[kDsyncRanks];
+#pragma unroll
+  for (int d = 1; d < kDsyncRanks; d++)  // (all loads first: they are independent)
+    if (d < n) x[d] = load8<false>(send + (size_t)((me + d) % n) * q.bytes + idx * 8, valid);
+#pragma unroll
+  for (int d = 1; d < kDsyncRanks; d++)  // (start with the next rank: the ranks do not all hit rank 0's page first)
+    if (d < n) ll_store(ll_slot(a.page[(me + d) % n], me, parity) + idx * 16, x[d], flag);
+}
+// all-to-all: rank p's line goes to place p of the receive buffer, the own block is copied locally
+__device__ __forceinline__ void ll_alltoall_collect(const DsyncLLArgs& a, const LLCall& q, LLShared& sh, uint32_t parity, uint32_t flag,
+                                                    size_t idx) {
+  const int me = a.me, n = a.n;
+  const uint32_t valid = q.bytes - idx * 8 >= 8 ? 8u : (uint32_t)(q.bytes - idx * 8);
+  char* recv = reinterpret_cast<char*>(q.recv);
+  store8<false>(recv + (size_t)me * q.bytes + idx * 8, load8<false>(reinterpret_cast<const char*>(q.send) + (size_t)me * q.bytes + idx * 8, valid),
+                valid);
+  uint64_t x[kDsyncRanks];
+  const uint32_t everyone = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
+  if (ll_gather(a, sh, everyone & ~(1u << me), parity, flag, idx, x)) {
+#pragma unroll
+    for (int p = 0; p < kDsyncRanks; p++)
+      if (p < n && p != me) store8<false>(recv + (size_t)p * q.bytes + idx * 8, x[p], valid);
+  }
+}
+// reduce-scatter: the peers' lines of block `me` and this rank's own, folded in rank order
+template <typename F>
+__device__ __forceinline__ void ll_reduce_scatter_collect(const DsyncLLArgs& a, const LLCall& q, LLShared& sh, uint32_t parity, uint32_t flag,
+                                                          size_t idx, F fold) {
+  const int me = a.me, n = a.n;
+  const uint32_t valid = q.bytes - idx * 8 >= 8 ? 8u : (uint32_t)(q.bytes - idx * 8);
+  const uint64_t mine8 = load8<false>(reinterpret_cast<const char*>(q.send) + (size_t)me * q.bytes + idx * 8, valid);
+  uint64_t x[kDsyncRanks];
+  const uint32_t everyone = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
+  if (ll_gather(a, sh, everyone & ~(1u << me), parity, flag, idx, x))
+    store8<false>(reinterpret_cast<char*>(q.recv) + idx * 8, fold([&x](int p) { return x[p]; }, mine8, me, n), valid);
+}
+
 // Every wave's stores have left; the block that finishes last advances the epoch and tells the host.  No exchange with the
 // peers: nobody reads this rank's buffers, and the slots are safe by the parity argument (kernels.h).
 __device__ __forceinline__ void ll_end(const DsyncLLArgs& a, LLShared& sh) {
@@ -342,6 +387,37 @@ __global__ __launch_bounds__(kBlock) void ll_copy_kernel(DsyncLLArgs a) {
     ll_copy_collect(a, q, sh, parity, flag, idx);
   }
   if (!gather) ll_wait_here(a, sh);
+  ll_end(a, sh);
+}
+
+// reduce-scatter: thread i owns bytes [8 i, 8 i + 8) of every block.  Every rank sends every peer a line (count > 0): no `here` words.
+template <typename T, int OP>
+__global__ __launch_bounds__(kBlock) void ll_reduce_scatter_kernel(DsyncLLArgs a) {
+  XMPI_SHARED(LLShared, sh);
+  ll_begin(a, sh);
+  const uint64_t epoch = sh.epoch;
+  const uint32_t parity = (uint32_t)(epoch & 1u), flag = (uint32_t)epoch ? (uint32_t)epoch : 1u;
+  const LLCall q{a.send, a.recv, a.bytes, a.coll, a.root};
+  const size_t idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx * 8 < a.bytes) {
+    ll_personal_push(a, q, parity, flag, idx);
+    ll_reduce_scatter_collect(a, q, sh, parity, flag, idx, LLFoldStatic<T, OP>{});
+  }
+  ll_end(a, sh);
+}
+
+// all-to-all: bytes only
+__global__ __launch_bounds__(kBlock) void ll_alltoall_kernel(DsyncLLArgs a) {
+  XMPI_SHARED(LLShared, sh);
+  ll_begin(a, sh);
+  const uint64_t epoch = sh.epoch;
+  const uint32_t parity = (uint32_t)(epoch & 1u), flag = (uint32_t)epoch ? (uint32_t)epoch : 1u;
+  const LLCall q{a.send, a.recv, a.bytes, a.coll, a.root};
+  const size_t idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx * 8 < a.bytes) {
+    ll_personal_push(a, q, parity, flag, idx);
+    ll_alltoall_collect(a, q, sh, parity, flag, idx);
+  }
   ll_end(a, sh);
 }
 
@@ -579,6 +655,16 @@ __global__ __launch_bounds__(kLLAgentBlock) void ll_agent_kernel(LLAgentArgs a) 
 
 template <typename T>
 hipError_t ll_op(const DsyncLLArgs& a, int op, dim3 grid, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
+  if (a.coll == LL_REDUCE_SCATTER) {
+    switch (op) {
+      case OP_SUM: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_SUM>), grid, dim3(kBlock), s, es, ee, a); break;
+      case OP_PROD: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_PROD>), grid, dim3(kBlock), s, es, ee, a); break;
+      case OP_MIN: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_MIN>), grid, dim3(kBlock), s, es, ee, a); break;
+      case OP_MAX: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_MAX>), grid, dim3(kBlock), s, es, ee, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (op) {
     case OP_SUM: XMPI_LAUNCH((ll_reduce_kernel<T, OP_SUM>), grid, dim3(kBlock), s, es, ee, a); break;
     case OP_PROD: XMPI_LAUNCH((ll_reduce_kernel<T, OP_PROD>), grid, dim3(kBlock), s, es, ee, a); break;
@@ -600,7 +686,11 @@ hipError_t launch_dsync_ll(const DsyncLLArgs& a, int dtype, int op, hipStream_t 
     XMPI_LAUNCH(ll_copy_kernel, grid, dim3(kBlock), s, es, ee, a);
     return hipGetLastError();
   }
-  if (a.coll != LL_ALLREDUCE && a.coll != LL_REDUCE) return hipErrorInvalidValue;
+  if (a.coll == LL_ALLTOALL) {
+    XMPI_LAUNCH(ll_alltoall_kernel, grid, dim3(kBlock), s, es, ee, a);
+    return hipGetLastError();
+  }
+  if (a.coll != LL_ALLREDUCE && a.coll != LL_REDUCE && a.coll != LL_REDUCE_SCATTER) return hipErrorInvalidValue;
   switch (dtype) {
     case DT_U8: return ll_op<uint8_t>(a, op, grid, s, es, ee);
     case DT_I32: return ll_op<int32_t>(a, op, grid, s, es, ee);

@@ -620,6 +620,58 @@ void build_reduce_direct(Builder& b) {
   }
 }
 
+// ---- reduce-scatter / all-to-all over the full mesh: blocks of P.count elements, block j belongs to rank j ------------------
+
+// the first half of build_reduce_scatter_gather with blocks for chunks: my block j goes to rank j, block `me` of everybody is
+// folded in rank order into the receive buffer
+void build_reduce_scatter_direct(Builder& b) {
+  const PlanParams& P = b.P;
+  const int N = P.size, r = P.rank;
+  const size_t pe = piece_elems_of(P);
+  const int L = std::max(1, P.lanes);
+  auto block = [&](int j) { return pieces_of((size_t)j * P.count, (size_t)(j + 1) * P.count, pe); };
+  for (int d = 1; d < N; d++) {
+    const int j = (r + d) % N;
+    const std::vector<Atom> pcs = block(j);
+    for (size_t p = 0; p < pcs.size(); p++) b.send(j, (int)(p % (size_t)L), BUF_SEND, pcs[p]);
+  }
+  const std::vector<Atom> mine = block(r);
+  for (size_t p = 0; p < mine.size(); p++) {
+    const int lane = (int)(p % (size_t)L);
+    std::vector<int> srcs;
+    for (int q = 0; q < N; q++) srcs.push_back(q == r ? -1 : b.recv_hold(q, lane, mine[p].count));
+    Step s;
+    s.kind = STEP_REDUCE_N;
+    s.src_buf = BUF_SEND; s.src_off = mine[p].off * b.es;
+    s.dst_buf = BUF_RECV; s.dst_off = (mine[p].off - (size_t)r * P.count) * b.es;
+    s.bytes = mine[p].count * b.es;
+    s.nsrcs = N;
+    for (int i = 0; i < N; i++) s.srcs[i] = srcs[(size_t)i];
+    b.emit(s, true, true);
+  }
+}
+
+// the helloworld exchange (helloworld.go:53-81) as a table: my block j goes to rank j, rank j's block for me lands in place j
+void build_alltoall_direct(Builder& b) {
+  const PlanParams& P = b.P;
+  const int N = P.size, r = P.rank;
+  const size_t pe = piece_elems_of(P);
+  const int L = std::max(1, P.lanes);
+  b.local_copy(BUF_SEND, (size_t)r * P.count, BUF_RECV, (size_t)r * P.count, P.count);
+  const std::vector<Atom> pcs = pieces_of(0, P.count, pe);  // of one block
+  for (size_t p = 0; p < pcs.size(); p++) {
+    const int lane = (int)(p % (size_t)L);
+    for (int d = 1; d < N; d++) {
+      const int j = (r + d) % N;
+      b.send(j, lane, BUF_SEND, Atom{(size_t)j * P.count + pcs[p].off, pcs[p].count});
+    }
+    for (int d = 1; d < N; d++) {
+      const int j = (r + N - d) % N;
+      b.recv_copy(j, lane, BUF_RECV, (size_t)j * P.count + pcs[p].off, pcs[p].count);
+    }
+  }
+}
+
 bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 
 }  // namespace
@@ -720,6 +772,14 @@ int build_plan(const PlanParams& p, Plan* out) {
       if (algo == XMPI_ALGO_TREE) build_reduce_tree(b);
       else if (algo == XMPI_ALGO_DIRECT) build_reduce_direct(b);
       else return XMPI_ERR_UNSUPPORTED;
+      break;
+    case COLL_REDUCE_SCATTER:  // (out of place only: the hazard tracker keeps send and receive offsets apart)
+    case COLL_ALLTOALL:
+      if (algo == XMPI_ALGO_AUTO) algo = XMPI_ALGO_DIRECT;
+      if (algo != XMPI_ALGO_DIRECT) return XMPI_ERR_UNSUPPORTED;
+      b.send_shift = (size_t)1 << 62;
+      if (p.coll == COLL_REDUCE_SCATTER) build_reduce_scatter_direct(b);
+      else build_alltoall_direct(b);
       break;
     default:
       return XMPI_ERR_ARG;

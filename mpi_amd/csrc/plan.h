@@ -27,7 +27,20 @@ enum StepKind : int {
 };
 
 enum BufId : int { BUF_SEND = 0, BUF_RECV = 1, BUF_TEMP = 2 };
-enum CollKind : int { COLL_ALLREDUCE = 0, COLL_ALLGATHER = 1, COLL_BCAST = 2, COLL_REDUCE = 3 };
+enum CollKind : int { COLL_ALLREDUCE = 0, COLL_ALLGATHER = 1, COLL_BCAST = 2, COLL_REDUCE = 3, COLL_REDUCE_SCATTER = 4, COLL_ALLTOALL = 5, COLL_COUNT = 6 };
+constexpr int kTunedColls = 4;  // the tuner's table, tune_rejected and xmpi_init's self-check know the first four only
+
+// What one rank's send / receive buffer of a collective holds, in bytes: `unit` = count x element size -- the whole message
+// (allreduce, bcast, reduce), one rank's block (allgather) or the block one rank gives to ONE peer (reduce-scatter, all-to-all).
+inline size_t coll_send_bytes(int coll, int size, size_t unit) {
+  return (coll == COLL_REDUCE_SCATTER || coll == COLL_ALLTOALL) ? unit * (size_t)size : unit;
+}
+inline size_t coll_recv_bytes(int coll, int size, size_t unit) {
+  return (coll == COLL_ALLGATHER || coll == COLL_ALLTOALL) ? unit * (size_t)size : unit;
+}
+// every rank gives every peer a different block (never in place: a block would be overwritten before its reader has it)
+inline bool coll_personal(int coll) { return coll == COLL_REDUCE_SCATTER || coll == COLL_ALLTOALL; }
+inline bool coll_reduces(int coll) { return coll == COLL_ALLREDUCE || coll == COLL_REDUCE || coll == COLL_REDUCE_SCATTER; }
 
 constexpr int kMaxDeps = 18;  // >= kMaxRanks + 2: a write may follow one read per peer (one-shot, in place)
 constexpr int kMaxSrcs = 16;
@@ -56,7 +69,7 @@ struct PlanParams {
   int size = 1;
   int rank = 0;
   int root = 0;
-  size_t count = 0;      // elements (allgather: per rank)
+  size_t count = 0;      // elements (allgather: per rank; reduce-scatter, all-to-all: per block)
   size_t elem_size = 4;  // bytes
   int channels = 1;      // ring channels (each a different Hamiltonian cycle of the mesh)
   int lanes = 2;         // FIFO lanes per ordered rank pair

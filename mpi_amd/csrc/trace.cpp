@@ -53,8 +53,8 @@ void roctx_pop() {
 }
 
 const char* coll_name(int coll) {
-  static const char* const names[] = {"allreduce", "allgather", "bcast", "reduce"};  // plan.h CollKind
-  return coll >= 0 && coll < 4 ? names[coll] : "?";
+  static const char* const names[] = {"allreduce", "allgather", "bcast", "reduce", "reduce_scatter", "alltoall"};  // plan.h CollKind
+  return coll >= 0 && coll < 6 ? names[coll] : "?";
 }
 const char* algo_name(int algo) {
   static const char* const names[] = {"auto", "ring", "rhd", "direct", "tree", "zcopy", "zpush", "ll", "ring_push", "rhd_push", "tree_push"};  // xmpi.h xmpi_algo

@@ -125,7 +125,7 @@ struct AnswerCheck {
     (void)hipGetLastError();
     send = recv = expect = expect2 = nullptr;
   }
-  size_t recv_bytes(int coll, size_t per_rank) const { return coll == COLL_ALLGATHER ? per_rank * (size_t)c->size : per_rank; }
+  size_t recv_bytes(int coll, size_t per_rank) const { return coll_recv_bytes(coll, c->size, per_rank); }
   // `expect` = what `coll` over `per_rank` bytes per rank (root 0) must leave in the receive buffer.  The pattern is a function of
   // the element's index: a shorter message is a prefix of a longer one's, so the sum and the broadcast are computed once, at `cap`.
   int expect_for(int coll, size_t per_rank) {

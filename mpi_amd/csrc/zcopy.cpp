@@ -296,8 +296,8 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
   *done = false;
   const int N = c->size, me = c->rank;
   const size_t es = xmpi_dtype_size((xmpi_dtype)dtype);
-  const size_t send_bytes = count * es;
-  const size_t recv_bytes = (coll == COLL_ALLGATHER) ? send_bytes * (size_t)N : send_bytes;
+  const size_t unit = count * es;  // the message; reduce-scatter, all-to-all: the block one rank gives one peer
+  const size_t send_bytes = coll_send_bytes(coll, N, unit), recv_bytes = coll_recv_bytes(coll, N, unit);
   const bool recv_significant = (coll != COLL_REDUCE) || me == root;
 
   // 1. publish what the peers need to reach my buffers
@@ -311,7 +311,7 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
   mine->fresh = fresh ? 1 : 0;
   mine->in_place = (sendbuf == recvbuf) ? 1 : 0;
   {
-    const bool reduces = coll == COLL_ALLREDUCE || coll == COLL_REDUCE, rooted = coll == COLL_BCAST || coll == COLL_REDUCE;
+    const bool reduces = coll_reduces(coll), rooted = coll == COLL_BCAST || coll == COLL_REDUCE;
     uint64_t h = 0x9E3779B97F4A7C15ull;
     for (uint64_t v : {(uint64_t)coll + 1, (uint64_t)(push ? 2 : 1), (uint64_t)send_bytes, reduces ? (uint64_t)dtype + 1 : 0,
                        reduces ? (uint64_t)op + 1 : 0, rooted ? (uint64_t)root + 1 : 0, (uint64_t)iters}) {
@@ -510,6 +510,31 @@ static int zc_run(xmpi_comm* c, int coll, int root, const void* sendbuf, void* r
         ev_put(c, ev.second, true);
       }
     }
+  } else if (coll == COLL_REDUCE_SCATTER) {  // block `me` of everybody's send buffer, folded in rank order into my receive buffer
+    const void* srcs[kMaxRanks];
+    for (int p = 0; p < N; p++) srcs[p] = psend[p] + (size_t)me * unit;
+    void* d1[1] = {precv[me]};
+    rc = L.begin((size_t)(N + 1) * unit);
+    if (rc) return rc;
+    XMPI_HIP(launch_reduce_n_multi(d1, 1, srcs, N, count, dtype, op, s, L.start, L.stop));
+    rc = L.finish();
+    if (rc) return rc;
+  } else if (coll == COLL_ALLTOALL) {  // my block q into place `me` of rank q's receive buffer: N pairs, one launch
+    static_assert(kMaxRanks <= kMaxBatch, "one batch holds a pair per rank");
+    void* dst[kMaxBatch];
+    const void* src[kMaxBatch];
+    size_t bytes[kMaxBatch];
+    for (int d = 0; d < N; d++) {
+      const int q = (me + d) % N;
+      dst[d] = precv[q] + (size_t)me * unit;
+      src[d] = psend[me] + (size_t)q * unit;
+      bytes[d] = unit;
+    }
+    rc = L.begin(2 * (size_t)N * unit);
+    if (rc) return rc;
+    XMPI_HIP(launch_copy_batch(dst, nullptr, src, bytes, N, s, L.start, L.stop));
+    rc = L.finish();
+    if (rc) return rc;
   } else if (coll == COLL_ALLGATHER) {
     void* dsts[kMaxRanks];
     int nd = 0;

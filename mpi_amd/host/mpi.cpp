@@ -118,6 +118,17 @@ Error Allgather(const Data& send, Data recv) {
   Collective* c = collective_or_null();
   return c ? c->Allgather(send, recv) : no_collectives();
 }
+Error ReduceScatter(const Data& send, Data recv, xmpi_op op) {
+  Collective* c = collective_or_null();
+  return c ? c->ReduceScatter(send, recv, op) : no_collectives();
+}
+Error Alltoall(const Data& send, Data recv) {
+  Collective* c = collective_or_null();
+  return c ? c->Alltoall(send, recv) : no_collectives();
+}
+// (a backend that has the four older collectives need not have these two)
+Error Collective::ReduceScatter(const Data&, Data, xmpi_op) { return Error(XMPI_ERR_UNSUPPORTED, "mpi reduce_scatter: unsupported by this backend"); }
+Error Collective::Alltoall(const Data&, Data) { return Error(XMPI_ERR_UNSUPPORTED, "mpi alltoall: unsupported by this backend"); }
 Error Barrier() {
   Collective* c = collective_or_null();
   return c ? c->Barrier() : no_collectives();
@@ -222,6 +233,31 @@ Error XGMI::Allgather(const Data& send, Data recv) {
                    "mpi allgather");
 }
 
+// `send` holds Size() equal blocks; the schedules that exist for the two: zcopy | ll | direct (reduce-scatter: | zpush), else the library's choice
+static Error blocks_of(const Data& send, int size, size_t* block, const char* where) {
+  if (size < 1 || send.count % (size_t)size != 0)
+    return Error(XMPI_ERR_ARG, std::string(where) + ": the send buffer holds " + std::to_string(send.count) + " elements, not one block per rank");
+  *block = send.count / (size_t)size;
+  return Error();
+}
+static int personal_algo(int algo, bool reduce) {
+  return algo == XMPI_ALGO_ZCOPY || algo == XMPI_ALGO_LL || algo == XMPI_ALGO_DIRECT || (reduce && algo == XMPI_ALGO_ZPUSH) ? algo : (int)XMPI_ALGO_AUTO;
+}
+
+Error XGMI::ReduceScatter(const Data& send, Data recv, xmpi_op op) {
+  size_t block = 0;
+  if (Error err = blocks_of(send, Size(), &block, "mpi reduce_scatter")) return err;
+  if (recv.resize) recv.resize(recv.owner, block, &recv);
+  return from_code(xmpi_reduce_scatter(comm_, send.ptr, recv.ptr, block, send.dtype, op, personal_algo(Algo, true)), "mpi reduce_scatter");
+}
+
+Error XGMI::Alltoall(const Data& send, Data recv) {
+  size_t block = 0;
+  if (Error err = blocks_of(send, Size(), &block, "mpi alltoall")) return err;
+  if (recv.resize) recv.resize(recv.owner, send.count, &recv);
+  return from_code(xmpi_alltoall(comm_, send.ptr, recv.ptr, block, send.dtype, personal_algo(Algo, false)), "mpi alltoall");
+}
+
 Error XGMI::Barrier() { return from_code(xmpi_barrier(comm_), "mpi barrier"); }
 
 Error XGMI::IAllreduce(const Data& send, Data recv, xmpi_op op, xmpi_request** req) {
@@ -243,6 +279,17 @@ Error XGMI::BcastOnStream(Data buf, int root, void* stream) {
 }
 Error XGMI::ReduceOnStream(const Data& send, Data recv, xmpi_op op, int root, void* stream) {
   return from_code(xmpi_reduce_on_stream(comm_, send.ptr, recv.ptr, send.count, send.dtype, op, root, stream), "mpi reduce");
+}
+
+Error XGMI::ReduceScatterOnStream(const Data& send, Data recv, xmpi_op op, void* stream) {
+  size_t block = 0;
+  if (Error err = blocks_of(send, Size(), &block, "mpi reduce_scatter")) return err;
+  return from_code(xmpi_reduce_scatter_on_stream(comm_, send.ptr, recv.ptr, block, send.dtype, op, stream), "mpi reduce_scatter");
+}
+Error XGMI::AlltoallOnStream(const Data& send, Data recv, void* stream) {
+  size_t block = 0;
+  if (Error err = blocks_of(send, Size(), &block, "mpi alltoall")) return err;
+  return from_code(xmpi_alltoall_on_stream(comm_, send.ptr, recv.ptr, block, send.dtype, stream), "mpi alltoall");
 }
 
 Error XGMI::GraphBegin(void* stream) { return from_code(xmpi_graph_begin(comm_, stream), "mpi graph begin"); }

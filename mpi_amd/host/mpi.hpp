@@ -18,7 +18,7 @@
 //   type Network (TCP backend)       network.go      class XGMI (HBM windows over xGMI, via libxmpi.so);
 //                                                    class Network (network.hpp): the reference's own TCP + gob
 //                                                    protocol, wire-compatible, for CPU / mixed / multi-node ranks
-//   //func AllReduce() {}            mpi.go:130      mpi::Allreduce / Bcast / Reduce / Allgather
+//   //func AllReduce() {}            mpi.go:130      mpi::Allreduce / Bcast / Reduce / Allgather / ReduceScatter / Alltoall
 //                                                    (optional Collective interface, cf. the unused
 //                                                     isAllReducer probe at mpi.go:69-71)
 // `data interface{}` becomes a typed view (Data) over host or HBM memory: the reference types the
@@ -115,6 +115,11 @@ class Collective {
   virtual Error Allreduce(const Data& send, Data recv, xmpi_op op) = 0;
   virtual Error Allgather(const Data& send, Data recv) = 0;
   virtual Error Barrier() = 0;
+  // Every rank gives every peer a different block: `send` holds Size() equal blocks, block j is for rank j.  ReduceScatter: recv
+  // (one block) = op over the ranks, in rank order, of their block `me`; Alltoall (the exchange of helloworld.go:53-81 as one call):
+  // recv (Size() blocks) = block `me` of rank 0, of rank 1, ...  A backend that does not have them says so.
+  virtual Error ReduceScatter(const Data& send, Data recv, xmpi_op op);
+  virtual Error Alltoall(const Data& send, Data recv);
 };
 
 // flags.go:10-14
@@ -142,6 +147,8 @@ Error Bcast(Data buf, int root);
 Error Reduce(const Data& send, Data recv, xmpi_op op, int root);
 Error Allreduce(const Data& send, Data recv, xmpi_op op = XMPI_SUM);
 Error Allgather(const Data& send, Data recv);
+Error ReduceScatter(const Data& send, Data recv, xmpi_op op = XMPI_SUM);
+Error Alltoall(const Data& send, Data recv);
 Error Barrier();
 
 // The MI355X backend: replaces type Network (network.go:25-39).  Zero-valued fields are taken from
@@ -166,6 +173,8 @@ class XGMI : public Interface, public Collective {
   Error Reduce(const Data& send, Data recv, xmpi_op op, int root) override;
   Error Allreduce(const Data& send, Data recv, xmpi_op op) override;
   Error Allgather(const Data& send, Data recv) override;
+  Error ReduceScatter(const Data& send, Data recv, xmpi_op op) override;
+  Error Alltoall(const Data& send, Data recv) override;
   Error Barrier() override;
 
   // The Send / Wait pair the reference sketches in a comment (mpi.go:132-152): SendNoWait returns once
@@ -189,6 +198,8 @@ class XGMI : public Interface, public Collective {
   Error AllgatherOnStream(const Data& send, Data recv, void* stream);
   Error BcastOnStream(Data buf, int root, void* stream);
   Error ReduceOnStream(const Data& send, Data recv, xmpi_op op, int root, void* stream);
+  Error ReduceScatterOnStream(const Data& send, Data recv, xmpi_op op, void* stream);
+  Error AlltoallOnStream(const Data& send, Data recv, void* stream);
   // hipGraph capture of what is enqueued on `stream` between GraphBegin and GraphEnd; GraphLaunch replays it
   Error GraphBegin(void* stream);
   Error GraphEnd(void* stream, void** graph);

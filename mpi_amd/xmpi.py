@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmpi.so")
 U8, I32, I64, F16, F32, F64, BF16 = range(7)
 SUM, PROD, MIN, MAX = range(4)
 ALGO_AUTO, ALGO_RING, ALGO_RHD, ALGO_DIRECT, ALGO_TREE, ALGO_ZCOPY, ALGO_ZPUSH, ALGO_LL, ALGO_RING_PUSH, ALGO_RHD_PUSH, ALGO_TREE_PUSH = range(11)
-COLL_ALLREDUCE, COLL_ALLGATHER, COLL_BCAST, COLL_REDUCE = range(4)
+COLL_ALLREDUCE, COLL_ALLGATHER, COLL_BCAST, COLL_REDUCE, COLL_REDUCE_SCATTER, COLL_ALLTOALL = range(6)
 PAT_UNIFORM, PAT_INDEX, PAT_CONST, PAT_SIGNED = range(4)
 PROF_REDUCE2, PROF_REDUCEN, PROF_COPY, PROF_PEER, PROF_ZCOPY = range(5)
 
@@ -55,6 +55,8 @@ SYMBOLS = [
     ("xmpi_reduce", _I, [_P, _P, _P, _Z, _I, _I, _I, _I]),
     ("xmpi_allreduce", _I, [_P, _P, _P, _Z, _I, _I, _I]),
     ("xmpi_allgather", _I, [_P, _P, _P, _Z, _I, _I]),
+    ("xmpi_reduce_scatter", _I, [_P, _P, _P, _Z, _I, _I, _I]),
+    ("xmpi_alltoall", _I, [_P, _P, _P, _Z, _I, _I]),
     ("xmpi_reduce_local", _I, [_P, _P, _P, _P, _Z, _I, _I]),
     ("xmpi_reduce_local_n", _I, [_P, _P, C.POINTER(_P), _I, _Z, _I, _I]),
     ("xmpi_copy_local", _I, [_P, _P, _P, _Z]),
@@ -90,6 +92,8 @@ SYMBOLS = [
     ("xmpi_zc_chunk", _I, [_Z, _Z, _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),
     ("xmpi_allreduce_on_stream", _I, [_P, _P, _P, _Z, _I, _I, _P]),
     ("xmpi_allgather_on_stream", _I, [_P, _P, _P, _Z, _I, _P]),
+    ("xmpi_reduce_scatter_on_stream", _I, [_P, _P, _P, _Z, _I, _I, _P]),
+    ("xmpi_alltoall_on_stream", _I, [_P, _P, _P, _Z, _I, _P]),
     ("xmpi_bcast_on_stream", _I, [_P, _P, _Z, _I, _I, _P]),
     ("xmpi_reduce_on_stream", _I, [_P, _P, _P, _Z, _I, _I, _I, _P]),
     ("xmpi_stream_create", _P, [_P]),
@@ -388,6 +392,22 @@ class Comm:
     def reduce_on_stream(self, send, recv, count: int, dtype: int, op: int, root: int, stream=None) -> None:
         _check(lib().xmpi_reduce_on_stream(self.handle, _ptr(send), _ptr(recv), count, dtype, op, root, stream),
                "xmpi_reduce_on_stream")
+
+    def reduce_scatter(self, send, recv, count: int, dtype: int, op: int, algo: int = ALGO_AUTO) -> None:
+        """recv[0:count] = op over ranks (rank order) of their send[me*count:(me+1)*count]; count = elements per block"""
+        _check(lib().xmpi_reduce_scatter(self.handle, _ptr(send), _ptr(recv), count, dtype, op, algo), "xmpi_reduce_scatter")
+
+    def alltoall(self, send, recv, count: int, dtype: int, algo: int = ALGO_AUTO) -> None:
+        """recv[r*count:(r+1)*count] = rank r's send[me*count:(me+1)*count]; count = elements per block"""
+        _check(lib().xmpi_alltoall(self.handle, _ptr(send), _ptr(recv), count, dtype, algo), "xmpi_alltoall")
+
+    def reduce_scatter_on_stream(self, send, recv, count: int, dtype: int, op: int, stream=None) -> None:
+        _check(lib().xmpi_reduce_scatter_on_stream(self.handle, _ptr(send), _ptr(recv), count, dtype, op, stream),
+               "xmpi_reduce_scatter_on_stream")
+
+    def alltoall_on_stream(self, send, recv, count: int, dtype: int, stream=None) -> None:
+        _check(lib().xmpi_alltoall_on_stream(self.handle, _ptr(send), _ptr(recv), count, dtype, stream),
+               "xmpi_alltoall_on_stream")
 
     def allgather(self, send, recv, count: int, dtype: int, algo: int = ALGO_AUTO) -> None:
         _check(lib().xmpi_allgather(self.handle, _ptr(send), _ptr(recv), count, dtype, algo), "xmpi_allgather")

@@ -12,6 +12,7 @@
 #include "xmpi_oracle.h"
 
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 size_t oracle_dtype_size(int dtype) {

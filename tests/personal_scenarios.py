@@ -12,6 +12,7 @@ import numpy as np
 
 from mpi_amd import xmpi
 from oracle import oracle
+from tests import hard_inputs as hi
 
 RS, A2A = "reduce_scatter", "alltoall"
 DTYPES = (xmpi.U8, xmpi.I32, xmpi.I64, xmpi.F16, xmpi.F32, xmpi.F64, xmpi.BF16)
@@ -245,6 +246,99 @@ def sc_layout(comm, args):
         assert comm.get_param("zc_seq") > 0 and comm.get_param("dsync_launches") == 0, "the host-rendezvous fold was not what ran"
 
 
+_hard_blocks = {}  # (dtype, count, seed, size, op == PROD) -> block q of rank r's send buffer, for every q and r: computed once, never written
+
+
+def hard_blocks(dtype: int, count: int, seed: int, size: int, op: int):
+    """tests/hard_inputs.py data for the personalised collectives: block q of every rank's send buffer is one `special` job of its
+    own (seed + 100 q) -- all 256 ordered pairs of specials meet in EVERY rank's result, not only in rank 0's -- and dense(spread 1)
+    for a product"""
+    key = (dtype, count, seed, size, op == xmpi.PROD)
+    if key not in _hard_blocks:
+        blocks = [hi.rank_inputs(dtype, count, seed + 100 * q, size, op) for q in range(size)]  # [q][r]
+        for row in blocks:
+            for x in row:
+                x.setflags(write=False)
+        _hard_blocks[key] = blocks
+    return _hard_blocks[key]
+
+
+def hard_personal_case(comm, coll, dtype, count, algo, op=xmpi.SUM, seed=8000):
+    """one reduce-scatter (against oracle_reduce_ranks over block `me` of every rank's input, under same_floats) or all-to-all (byte
+    for byte: a copy touches no bit, a signalling NaN's payload and -0 included) of that data"""
+    me, size = comm.rank(), comm.size()
+    es = xmpi.DTYPE_SIZE[dtype]
+    npdt = xmpi.NUMPY_DTYPE[dtype]
+    blocks = hard_blocks(dtype, count, seed, size, op)
+    mine = np.concatenate([blocks[q][me] for q in range(size)])
+    what = f"{coll} of hard inputs {xmpi.DTYPE_NAME[dtype]} count={count} algo={algo} op={op} rank {me}/{size}"
+    rb = (count if coll == RS else size * count) * es
+    send, recv = comm.alloc(size * count * es).upload(mine), comm.alloc(rb + GUARD)
+    comm.memset(recv, 0xA5, rb + GUARD)
+    _call(comm, coll, send, recv, count, dtype, op, algo, None)
+    got = recv.download(npdt, rb // es)
+    if coll == RS:
+        hi.same_floats(got, oracle.reduce_ranks(blocks[me], dtype, op), dtype, op, what)
+    else:
+        assert got.tobytes() == b"".join(blocks[me][r].tobytes() for r in range(size)), f"{what}: bits changed on the way"
+    assert np.all(recv.download(np.uint8, GUARD, byte_offset=rb) == 0xA5), f"{what}: wrote past the receive buffer"
+    assert send.download(npdt, size * count).tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
+    send.free()
+    recv.free()
+
+
+def sc_hard(comm, args):
+    """reduce-scatter's rank-order claim where it can be seen (tests/hard_inputs.py): the four float types x {SUM, MIN, MAX} on
+    `special` data and PROD on dense(spread 1) data, 1003 elements per block (LL lines for every type, ragged) and 8209 (above
+    ll_bytes: packets, a tail, unaligned blocks), by every name, one kernel and meet / body / done -- the counters say which ran;
+    and all-to-all of special f32 / f16 data by every name, byte for byte"""
+    me, size = comm.rank(), comm.size()
+    counts = args.get("counts", [1003, 8209])
+    staged = bool(args.get("expect_staged"))
+    dsync = comm.get_param("dsync") == 1
+    names = ("zc_seq", "dsync_launches", "dsync_ll_launches", "dsync_split_launches", "ll_bytes")
+    counters = lambda: {k: comm.get_param(k) for k in names}
+    maxb = comm.get_param("ll_max_bytes")
+    split0 = comm.get_param("dsync_split_bytes")
+
+    def ran(algo, split, unit, b, a):
+        d = {k: a[k] - b[k] for k in names}
+        if staged:
+            return a["zc_seq"] == 0 and a["dsync_launches"] == 0
+        if not dsync:  # the host rendezvous (DIRECT: the staged table)
+            return a["dsync_launches"] == 0 and d["zc_seq"] == (0 if algo == xmpi.ALGO_DIRECT else 1)
+        if algo == xmpi.ALGO_DIRECT:
+            return d["dsync_launches"] == 0 and d["dsync_ll_launches"] == 0
+        if (algo == xmpi.ALGO_LL and unit <= maxb) or (algo == xmpi.ALGO_AUTO and unit <= b["ll_bytes"]):
+            return d["dsync_ll_launches"] == 1 and d["dsync_split_launches"] == 0
+        if algo == xmpi.ALGO_ZPUSH:
+            return d["dsync_ll_launches"] == 0 and d["dsync_launches"] >= 1
+        return d["dsync_ll_launches"] == 0 and ((d["dsync_split_launches"], d["dsync_launches"]) == ((1, 3) if split else (0, 1)))
+
+    n = 0
+    for split in (1, 0) if dsync else (None,):
+        if split is not None:
+            comm.set_param("dsync_split_bytes", split)
+        for algo in (xmpi.ALGO_AUTO, xmpi.ALGO_DIRECT) if staged else RS_ALGOS:
+            for dtype in hi.FLOATS:
+                for op in OPS:
+                    for count in counts:
+                        before = counters()
+                        hard_personal_case(comm, RS, dtype, count, algo, op)
+                        after = counters()
+                        n += 1
+                        assert ran(algo, split, count * xmpi.DTYPE_SIZE[dtype], before, after), \
+                            f"reduce_scatter algo={algo} split={split} {xmpi.DTYPE_NAME[dtype]} count={count}: another form ran, counters {before} -> {after}"
+        for algo in (xmpi.ALGO_AUTO, xmpi.ALGO_DIRECT) if staged else A2A_ALGOS:
+            for dtype in (xmpi.F32, xmpi.F16):
+                for count in counts:
+                    hard_personal_case(comm, A2A, dtype, count, algo)
+    if dsync:
+        comm.set_param("dsync_split_bytes", split0)
+    if me == 0:
+        print(f"personal hard: {n} reduce-scatters checked, each with its form confirmed by the counters")
+
+
 def sc_mismatch(comm, args):
     """ranks in different calls -- an all-to-all against a reduce-scatter over the same bytes, above the LL limit: every rank gets
     XMPI_ERR_ARG at once, nothing is moved.  (Virtual devices only.)"""
@@ -299,4 +393,4 @@ def sc_fullsize(comm, args):
 
 
 SCENARIOS = {"algos": sc_algos, "sweep": sc_sweep, "memory": sc_memory, "graph": sc_graph, "parity": sc_parity, "layout": sc_layout,
-             "mismatch": sc_mismatch, "fullsize": sc_fullsize}
+             "mismatch": sc_mismatch, "fullsize": sc_fullsize, "hard": sc_hard}

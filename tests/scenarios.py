@@ -12,6 +12,7 @@ import numpy as np
 
 from mpi_amd import xmpi
 from oracle import oracle
+from tests import hard_inputs as hi
 
 FLOATS = (xmpi.F16, xmpi.F32, xmpi.F64, xmpi.BF16)
 # per-element tolerance factor on sum_i |x_i| when the summation order differs from rank order
@@ -1170,6 +1171,16 @@ def sc_sched(comm, args):
             for dtype, count in ((xmpi.F32, 100003), (xmpi.F16, 70001)) + (() if quick else ((xmpi.F32, (1 << 20) + 1),)):
                 for inplace in (False, True):
                     same_bits_case(comm, dtype, count, pull, push, inplace)
+            # (an f32 sum of PAT_SIGNED is the same in every order: the leg above shows nothing for it.)  Dense data in every float
+            # type; and with specials planted, a sum and a selection
+            for dtype in FLOATS:
+                for count in args.get("hard_counts", [4099, 65536 + 5]):
+                    same_bits_case(comm, dtype, count, pull, push, False, data="dense")
+                same_bits_case(comm, dtype, 4099, pull, push, True, data="dense")
+                same_bits_case(comm, dtype, 4099, pull, push, False, data="special")
+                same_bits_case(comm, dtype, 4099, pull, push, True, data="special", op=xmpi.MIN)
+        if (channels, grid) in ((0, 0), (2, 3)):
+            hard_stepped(comm, args.get("hard_counts", [4099, 65536 + 5]))
         # several of them enqueued back to back, nobody waiting in between: the push forms' landing block is used again by the next
         # collective before the host has seen the last one end
         for algo in (xmpi.ALGO_RING_PUSH, xmpi.ALGO_RHD_PUSH):
@@ -1376,21 +1387,30 @@ def reduce_case(comm, dtype, count, root, algo, op=xmpi.SUM, pat=xmpi.PAT_SIGNED
     return out
 
 
-def same_bits_case(comm, dtype, count, pull, push, inplace):
-    """the same inputs through the pull and the push form of a schedule: bit-identical results on every rank"""
-    rank = comm.rank()
+def same_bits_case(comm, dtype, count, pull, push, inplace, data="signed", op=xmpi.SUM):
+    """the same inputs through the pull and the push form of a schedule: bit-identical results on every rank.  data: "signed"
+    (PAT_SIGNED: f32 / f64 sums of it are the same in every order), "dense" (tests/hard_inputs.py: another order or association
+    shows in every float type) or "special" (NaNs, infinities, signed zeros, subnormals planted).  Ring and halving run
+    ONE instantiation of the tile function in both forms, so even a NaN's bits agree; that rests on the compiler giving both the
+    same operand order where two NaNs meet -- the tree's forms, two instantiations, differ in exactly that, on the MI355X and
+    when compiled for the host (same_forms) -- and a compiler update may move it: a failure here that shows only NaN against NaN is that, not a fold
+    out of order"""
+    rank, size = comm.rank(), comm.size()
     es = xmpi.DTYPE_SIZE[dtype]
     out = []
     for algo in (pull, push):
         send = comm.alloc(count * es)
         recv = send if inplace else comm.alloc(count * es)
-        comm.fill(send, count, dtype, xmpi.PAT_SIGNED, 300 + rank)
-        comm.allreduce(send, recv, count, dtype, xmpi.SUM, algo)
+        if data == "signed":
+            comm.fill(send, count, dtype, xmpi.PAT_SIGNED, 300 + rank)
+        else:
+            send.upload(hard_case(dtype, count, 7300, size, op, data)[0][rank])
+        comm.allreduce(send, recv, count, dtype, op, algo)
         out.append(recv.download(np.uint8, count * es).tobytes())
         if not inplace:
             recv.free()
         send.free()
-    assert out[0] == out[1], f"allreduce {xmpi.DTYPE_NAME[dtype]} n={count} inplace={inplace}: algo {push} and algo {pull} differ in " \
+    assert out[0] == out[1], f"allreduce {xmpi.DTYPE_NAME[dtype]} n={count} inplace={inplace} data={data} op={op}: algo {push} and algo {pull} differ in " \
                              f"{sum(a != b for a, b in zip(out[0], out[1]))} bytes"
 
 
@@ -2972,6 +2992,302 @@ def sc_guard(comm, args):
             gfree(buf, nb)
 
 
+
+# ---- float inputs on which order and special values show (tests/hard_inputs.py) ----------------------------------------------------
+_hard_cases = {}  # (dtype, count, seed, size, op, kind) -> (every rank's input, the oracle's rank-order fold): computed once, never written
+
+
+def hard_case(dtype, count, seed, size, op, kind="special"):
+    key = (dtype, count, seed, size, op == xmpi.PROD, kind)  # (SUM, MIN and MAX share their inputs; a product has a spread of its own)
+    if key not in _hard_cases:
+        ins = hi.rank_inputs(dtype, count, seed, size, op, kind)
+        for x in ins:
+            x.setflags(write=False)
+        _hard_cases[key] = (ins, {})
+    ins, wants = _hard_cases[key]
+    if op not in wants:
+        wants[op] = oracle.reduce_ranks(ins, dtype, op)
+        wants[op].setflags(write=False)
+    return ins, wants[op]
+
+
+def hard_reduce_case(comm, dtype, count, op, algo, root=None, inplace=False, misalign=0, seed=7000, what=""):
+    """one allreduce (root None) or reduce of tests/hard_inputs.py data -- specials planted for SUM / MIN / MAX, dense(spread 1)
+    for PROD -- by a rank-order form: held to oracle_reduce_ranks under same_floats (MIN / MAX: every byte; SUM / PROD: the same NaN
+    positions, every other element byte for byte)"""
+    rank, size = comm.rank(), comm.size()
+    es = xmpi.DTYPE_SIZE[dtype]
+    shift = misalign * es
+    ins, want = hard_case(dtype, count, seed, size, op)
+    send = comm.alloc(count * es + shift)
+    recv = send if inplace else comm.alloc(count * es + shift)
+    send.upload(ins[rank], byte_offset=shift)
+    if not inplace:
+        comm.memset(recv, 0xA5, count * es + shift)
+    if root is None:
+        comm.allreduce(send.at(shift), recv.at(shift), count, dtype, op, algo)
+    else:
+        comm.reduce(send.at(shift), recv.at(shift) if rank == root else None, count, dtype, op, root, algo)
+    what = f"{what}: {'allreduce' if root is None else f'reduce root={root}'} {xmpi.DTYPE_NAME[dtype]} n={count} op={op} algo={algo} inplace={inplace} misalign={misalign}"
+    if root is None or rank == root:
+        hi.same_floats(recv.download(xmpi.NUMPY_DTYPE[dtype], count, byte_offset=shift), want, dtype, op, what)
+    elif not inplace:
+        assert np.all(recv.download(np.uint8, count * es + shift) == 0xA5), f"{what}: wrote a non-root's buffer"
+    if not inplace:
+        assert send.download(xmpi.NUMPY_DTYPE[dtype], count, byte_offset=shift).tobytes() == ins[rank].tobytes(), f"{what}: sendbuf was modified"
+        recv.free()
+    send.free()
+
+
+def hard_unordered_reduce_case(comm, dtype, count, op, algo, root, what):
+    """a reduce that is NOT in rank order (the staged tree table): dense data within DESIGN's tolerance of the rank-order oracle
+    (check_reduced; MIN / MAX: its bits; a product in another order may underflow differently and is left to the rank-order forms),
+    special data under check_unordered"""
+    rank, size = comm.rank(), comm.size()
+    es = xmpi.DTYPE_SIZE[dtype]
+    if op == xmpi.PROD:
+        return 0
+    for kind, seed in (("dense", 7200), ("special", 7000)):
+        ins, want = hard_case(dtype, count, seed, size, op, kind)
+        send, recv = comm.alloc(count * es).upload(ins[rank]), comm.alloc(count * es)
+        comm.memset(recv, 0xA5, count * es)
+        comm.reduce(send, recv if rank == root else None, count, dtype, op, root, algo)
+        got = recv.download(xmpi.NUMPY_DTYPE[dtype], count)
+        where = f"{what}: reduce root={root} of {kind} data {xmpi.DTYPE_NAME[dtype]} n={count} op={op} algo={algo}"
+        if rank != root:
+            assert np.all(got.view(np.uint8) == 0xA5), f"{where}: wrote a non-root's buffer"
+        elif kind == "dense":
+            check_reduced(got, ins, dtype, op, False, where)
+        else:
+            check_unordered(got, ins, want, dtype, op, where)
+        assert send.download(np.uint8, count * es).tobytes() == ins[rank].tobytes(), f"{where}: sendbuf was modified"
+        send.free()
+        recv.free()
+    return 2
+
+
+def _hard_forms(comm, staged):
+    """(what, algorithm name, parameters for the call, counters afterwards -- a function of (counters before, counters after, bytes
+    per rank) that says whether the intended form ran) for every rank-order form of allreduce and reduce in this layout"""
+    if staged:  # XMPI_ZERO_COPY=0: the staged step tables (reduce2_batch); a zero-copy NAME would still ask for the zero-copy fold
+        nothing = lambda b, a, unit: a["zc_seq"] == 0 and a["dsync_launches"] == 0
+        # (reduce by AUTO is the TREE table below oneshot_bytes -- plan.cpp -- and folds in an order of its own: "tree_reduce")
+        return [("staged AUTO (allreduce: the DIRECT table; reduce: the TREE table)", xmpi.ALGO_AUTO, {"tree_reduce": 1}, nothing),
+                ("staged DIRECT", xmpi.ALGO_DIRECT, {}, nothing)]
+    if comm.get_param("dsync") != 1:  # the host rendezvous: one reduce_n_multi launch; LL names the library's own choice there
+        met = lambda b, a, unit: a["zc_seq"] == b["zc_seq"] + 1 and a["dsync_launches"] == 0
+        return [(f"host rendezvous, algo {algo}", algo, {}, met) for algo in (xmpi.ALGO_AUTO, xmpi.ALGO_LL, xmpi.ALGO_ZCOPY, xmpi.ALGO_ZPUSH)] + [
+            ("DIRECT", xmpi.ALGO_DIRECT, {}, lambda b, a, unit: a["zc_seq"] == b["zc_seq"] and a["dsync_launches"] == 0)]
+    maxb = comm.get_param("ll_max_bytes")
+    ll = lambda b, a: a["dsync_ll_launches"] - b["dsync_ll_launches"]
+    agent = lambda b, a: a["dsync_ll_agent"] - b["dsync_ll_agent"]
+    split = lambda b, a: a["dsync_split_launches"] - b["dsync_split_launches"]
+    launches = lambda b, a: a["dsync_launches"] - b["dsync_launches"]
+    one_kernel = lambda b, a, unit: launches(b, a) == 1 and split(b, a) == 0 and ll(b, a) == 0
+    split_form = lambda b, a, unit: split(b, a) == 1 and launches(b, a) == 3 and ll(b, a) == 0
+    forms = [
+        ("AUTO", xmpi.ALGO_AUTO, {}, lambda b, a, unit: (ll(b, a) == 1) if unit <= b["ll_bytes"] else (ll(b, a) == 0 and launches(b, a) >= 1)),
+        # (named LL above the slot limit is the fold, still rank order)
+        ("LL, launched", xmpi.ALGO_LL, {"agent_ll": 0}, lambda b, a, unit: (ll(b, a), agent(b, a)) == ((1, 0) if unit <= maxb else (0, 0)) and launches(b, a) >= 1),
+        ("ZCOPY, one kernel", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 0, "dsync_unroll": 1}, one_kernel),
+        ("ZCOPY, one kernel, unroll 2", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 0, "dsync_unroll": 2}, one_kernel),
+        ("ZCOPY, meet / body / done", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 1, "body_sys": 0}, split_form),
+        ("ZCOPY, meet / body / done, system-scope body", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 1, "body_sys": 1}, split_form),
+        ("ZPUSH", xmpi.ALGO_ZPUSH, {}, lambda b, a, unit: launches(b, a) >= 1 and ll(b, a) == 0 and a["dsync_sched_launches"] == b["dsync_sched_launches"]),
+        ("DIRECT", xmpi.ALGO_DIRECT, {}, lambda b, a, unit: launches(b, a) == 0 and ll(b, a) == 0),
+    ]
+    if comm.get_param("agent_ll") >= 1 and comm.get_param("ll_agent_us") > 0:  # (as _ll_agent_section: the agent is on in this job)
+        forms.insert(2, ("LL, by the agent", xmpi.ALGO_LL, {"agent_ll": 1, "agent_ll_bytes": maxb, "sync_first": 1},
+                         lambda b, a, unit: (ll(b, a), agent(b, a)) == ((1, 1) if unit <= maxb else (0, 0))))
+    return forms
+
+
+_HARD_COUNTERS = ("zc_seq", "dsync_launches", "dsync_ll_launches", "dsync_ll_agent", "dsync_split_launches", "dsync_sched_launches", "ll_bytes")
+
+
+def sc_hard_floats(comm, args):
+    """Every rank-order form of allreduce and reduce on inputs where the fold ORDER and SPECIAL values show (tests/hard_inputs.py):
+    per call `special` data for the four float types x {SUM, MIN, MAX} and dense(spread 1) data for PROD, against
+    oracle_reduce_ranks under same_floats; 1003 elements (LL lines for every type, ragged) and 8209 (above ll_bytes: packets, a
+    tail, an unaligned chunk); one in-place call one element into its buffer.  After every call the counters say that the form
+    that was meant is the one that ran.  Then the copies -- bcast, allgather -- of special f32 and f16 data by every name they
+    take: byte-identical, signalling NaNs' payloads and -0 included."""
+    rank, size = comm.rank(), comm.size()
+    counts = args.get("counts", [1003, 8209])
+    staged = bool(args.get("expect_staged"))
+    dsync = comm.get_param("dsync") == 1
+    counters = lambda: {k: comm.get_param(k) for k in _HARD_COUNTERS}
+    ncalls, ntree = [0], [0]
+    forms = _hard_forms(comm, staged)
+    for what, algo, params, ran in forms:
+        old = {k: comm.get_param(k) for k in params if k not in ("sync_first", "tree_reduce")}
+        for k in old:
+            comm.set_param(k, params[k])
+
+        def call(dtype, count, op, **kw):
+            if params.get("sync_first"):
+                comm.sync()  # (the agent takes a call only when the stream it would have been enqueued on is idle)
+            before = counters()
+            hard_reduce_case(comm, dtype, count, op, algo, what=what, **kw)
+            ncalls[0] += 1
+            after = counters()
+            assert ran(before, after, count * xmpi.DTYPE_SIZE[dtype]), \
+                f"{what}: another form ran ({xmpi.DTYPE_NAME[dtype]} n={count} op={op} {kw}): counters {before} -> {after}"
+
+        for dtype in FLOATS:
+            for op in (xmpi.SUM, xmpi.MIN, xmpi.MAX, xmpi.PROD):
+                for count in counts:
+                    call(dtype, count, op)
+                    for root in sorted({0, size // 2}):
+                        if params.get("tree_reduce"):
+                            # up to oneshot_bytes (1 MiB unless the environment says otherwise; written, not readable) the TREE table ...
+                            before = counters()
+                            ntree[0] += hard_unordered_reduce_case(comm, dtype, count, op, algo, root, what)
+                            assert ran(before, counters(), 0), f"{what}: another form ran"
+                            if size > 2:  # ... above it the DIRECT table, in rank order
+                                comm.set_param("oneshot_bytes", 0)
+                                call(dtype, count, op, root=root)
+                                comm.set_param("oneshot_bytes", 1 << 20)
+                        else:
+                            call(dtype, count, op, root=root)
+            call(dtype, counts[0], xmpi.SUM, inplace=True, misalign=1)
+        for k, v in old.items():
+            comm.set_param(k, v)
+    # copies must not touch bits
+    names_gather = [xmpi.ALGO_AUTO, xmpi.ALGO_DIRECT] if staged else [xmpi.ALGO_AUTO, xmpi.ALGO_LL, xmpi.ALGO_ZCOPY, xmpi.ALGO_RING, xmpi.ALGO_DIRECT] + (
+        [xmpi.ALGO_RING_PUSH] if dsync else [])
+    names_bcast = [xmpi.ALGO_AUTO, xmpi.ALGO_TREE, xmpi.ALGO_DIRECT] if staged else [xmpi.ALGO_AUTO, xmpi.ALGO_LL, xmpi.ALGO_ZCOPY, xmpi.ALGO_TREE,
+                                                                                     xmpi.ALGO_DIRECT] + ([xmpi.ALGO_TREE_PUSH] if dsync else [])
+    if comm.get_param("copy_engine") != 0:  # (bcast's full-mesh staged form is the default transport's: sc_bcast_reduce)
+        names_bcast.remove(xmpi.ALGO_DIRECT)
+    for dtype in (xmpi.F32, xmpi.F16):
+        es = xmpi.DTYPE_SIZE[dtype]
+        for count in counts:
+            ins = hard_case(dtype, count, 7100, size, xmpi.SUM)[0]
+            for algo in names_gather:
+                send, recv = comm.alloc(count * es).upload(ins[rank]), comm.alloc(count * es * size)
+                comm.memset(recv, 0x5A, count * es * size)
+                comm.allgather(send, recv, count, dtype, algo)
+                assert recv.download(np.uint8, count * es * size).tobytes() == b"".join(x.tobytes() for x in ins), \
+                    f"allgather of special {xmpi.DTYPE_NAME[dtype]} data n={count} algo={algo}: bits changed"
+                send.free()
+                recv.free()
+            for push_bytes in (256 << 10, 0):  # (zero-copy bcast: the root pushes to everyone / scatter + allgather of the chunks)
+                comm.set_param("zc_bcast_push_bytes", push_bytes)
+                for algo in names_bcast:
+                    for root in sorted({0, size // 2}):
+                        buf = comm.alloc(count * es).upload(ins[rank])
+                        comm.bcast(buf, count, dtype, root, algo)
+                        assert buf.download(np.uint8, count * es).tobytes() == ins[root].tobytes(), \
+                            f"bcast of special {xmpi.DTYPE_NAME[dtype]} data n={count} root={root} algo={algo}: bits changed"
+                        buf.free()
+            comm.set_param("zc_bcast_push_bytes", 256 << 10)
+    if rank == 0:
+        print(f"hard_floats: {ncalls[0]} reductions held to the rank-order oracle ({ntree[0]} more, by the staged tree, to what holds in any order), "
+              f"each with its form confirmed by the counters: {', '.join(f[0] for f in forms)}")
+
+
+def check_unordered(got, ins, want, dtype, op, what):
+    """what holds of a fold of SPECIAL data in ANY order, against the rank-order oracle `want`: MIN / MAX equal it in VALUE in every
+    column in which no rank's input is NaN (a selection does not depend on the order there, up to the sign of a zero); a SUM is
+    NaN in every column in which some rank's input is"""
+    nan_in = np.any([hi.is_nan(x, dtype) for x in ins], axis=0)
+    if op == xmpi.SUM:
+        lost = nan_in & ~hi.is_nan(got, dtype)
+        assert not np.any(lost), f"{what}: {int(np.sum(lost))} columns with a NaN among the inputs are no NaN in the sum, first at {int(np.nonzero(lost)[0][0])}"
+        return
+    with np.errstate(invalid="ignore"):
+        bad = ~nan_in & (oracle.as_float64(got, dtype) != oracle.as_float64(want, dtype))
+    assert not np.any(bad), f"{what}: {int(np.sum(bad))} columns without a NaN differ in value from the oracle, first at {int(np.nonzero(bad)[0][0])}"
+
+
+def same_forms(bits, what, dtype, tree_sum_of_specials=False):
+    """a schedule's push form against its pull form (the same operands in the same association): every byte, a NaN's included.
+    One exception, measured: the tree's SUM where TWO NaNs meet in a column.  Its pull form is two passes of the two-operand tile
+    function, its push form one pass of the three-operand one -- different instantiations, and which NaN's payload an addition
+    returns is settled per instantiation by the compiler (operand order; on gfx950 also whether the adds of a packet end up as
+    v_pk_add_f32 or v_add_f32 -- the f32 stepped kernel holds both).  On an MI355X: f32, 3 and 4 ranks, 10 of 4099 columns; compiled
+    for the host (tests/devsim): f16, 4 ranks, 24 of 4099; a NaN on both sides in every one.  For that case the NaN positions
+    are compared and every other element byte for byte (hard_inputs.same_floats); ring and halving, one instantiation in both
+    forms, and the tree on everything else keep the bytes."""
+    for pull, push in ((xmpi.ALGO_RING, xmpi.ALGO_RING_PUSH), (xmpi.ALGO_RHD, xmpi.ALGO_RHD_PUSH), (xmpi.ALGO_TREE, xmpi.ALGO_TREE_PUSH)):
+        if tree_sum_of_specials and pull == xmpi.ALGO_TREE:
+            npdt = xmpi.NUMPY_DTYPE[dtype]
+            hi.same_floats(np.frombuffer(bits[push], dtype=npdt), np.frombuffer(bits[pull], dtype=npdt), dtype, xmpi.SUM, f"{what}: algo {push} against algo {pull}")
+            continue
+        assert bits[pull] == bits[push], f"{what}: algo {push} and algo {pull} differ in {sum(a != b for a, b in zip(bits[pull], bits[push]))} bytes"
+
+
+def hard_stepped(comm, counts):
+    """The stepped schedules (ring, halving, tree; pull and push) fold in an order of their own, so the rank-order oracle applies
+    in part.  Dense data: within DESIGN's tolerances (TOL) of it.  Special data: every rank holds the same result (an 8-byte
+    checksum of the NaN-normalised bits, gathered through DIRECT), and MIN / MAX equal the oracle's VALUE in every column in which
+    no rank's input is NaN (a selection does not depend on the order there, up to the sign of a zero) -- at most 25 % of the
+    columns are left out at 4099 elements (about 11 % by the planting rule) --, a SUM is NaN wherever an input is (check_unordered);
+    and a schedule's push form gives its pull form's bytes (same_forms)."""
+    rank, size = comm.rank(), comm.size()
+    allreduces = (xmpi.ALGO_RING, xmpi.ALGO_RHD, xmpi.ALGO_RING_PUSH, xmpi.ALGO_RHD_PUSH)
+    trees = (xmpi.ALGO_TREE, xmpi.ALGO_TREE_PUSH)
+    sums = comm.alloc(8 * size)
+
+    def run(dtype, count, op, algo, ins, root=None):
+        es = xmpi.DTYPE_SIZE[dtype]
+        send, recv = comm.alloc(count * es).upload(ins[rank]), comm.alloc(count * es)
+        comm.memset(recv, 0x3C, count * es)
+        if root is None:
+            comm.allreduce(send, recv, count, dtype, op, algo)
+        else:
+            comm.reduce(send, recv if rank == root else None, count, dtype, op, root, algo)
+        got = recv.download(xmpi.NUMPY_DTYPE[dtype], count)
+        assert send.download(np.uint8, count * es).tobytes() == ins[rank].tobytes(), "sendbuf was modified"
+        if root is not None and rank != root:
+            assert np.all(got.view(np.uint8) == 0x3C), "reduce wrote a non-root's buffer"
+        send.free()
+        recv.free()
+        return got
+
+    for dtype in FLOATS:
+        for count in counts:
+            # dense data, every operation: the rank-order oracle within the stated tolerance (MIN / MAX: the very bits)
+            for op in (xmpi.SUM, xmpi.MIN, xmpi.MAX):
+                ins, _ = hard_case(dtype, count, 7200, size, op, "dense")
+                bits = {}
+                for algo in allreduces:
+                    got = run(dtype, count, op, algo, ins)
+                    check_reduced(got, ins, dtype, op, False, f"dense data, allreduce algo={algo} {xmpi.DTYPE_NAME[dtype]} n={count}")
+                    bits[algo] = got.tobytes()
+                for algo in trees:
+                    got = run(dtype, count, op, algo, ins, root=size // 2)
+                    if rank == size // 2:
+                        check_reduced(got, ins, dtype, op, False, f"dense data, reduce algo={algo} {xmpi.DTYPE_NAME[dtype]} n={count}")
+                    bits[algo] = got.tobytes()
+                same_forms(bits, f"dense data {xmpi.DTYPE_NAME[dtype]} n={count} op={op}", dtype)
+            # special data
+            for op in (xmpi.SUM, xmpi.MIN, xmpi.MAX):
+                ins, want = hard_case(dtype, count, 7000, size, op)
+                if count == 4099:
+                    skipped = float(np.mean(np.any([hi.is_nan(x, dtype) for x in ins], axis=0)))
+                    assert skipped <= 0.25, f"{100 * skipped:.1f} % of the columns hold a NaN: too many to leave out"
+                bits = {}
+                for algo in allreduces + trees:
+                    root = size // 2 if algo in trees else None
+                    got = run(dtype, count, op, algo, ins, root=root)
+                    bits[algo] = got.tobytes()
+                    what = f"special data, algo={algo} {xmpi.DTYPE_NAME[dtype]} n={count} op={op}"
+                    if root is None:  # every rank holds the same result
+                        mine = np.array([oracle.checksum(hi.nan_normalised(got, dtype))], dtype=np.uint64)
+                        sums.upload(mine.view(np.int64))
+                        every = comm.alloc(8 * size)
+                        comm.allgather(sums, every, 1, xmpi.I64, xmpi.ALGO_DIRECT)
+                        seen = every.download(np.int64, size).view(np.uint64)
+                        every.free()
+                        assert np.all(seen == mine[0]), f"{what}: the ranks hold different results (checksums {[hex(int(x)) for x in seen]})"
+                    if root is None or rank == root:
+                        check_unordered(got, ins, want, dtype, op, what)
+                same_forms(bits, f"special data {xmpi.DTYPE_NAME[dtype]} n={count} op={op}", dtype, tree_sum_of_specials=op == xmpi.SUM)
+    sums.free()
+
+
 SCENARIOS = {
     "guard": sc_guard,
     "corrupt": sc_corrupt,
@@ -3004,4 +3320,5 @@ SCENARIOS = {
     "nonblocking": sc_nonblocking,
     "stream_ordered": sc_stream_ordered,
     "lifecycle_stress": sc_lifecycle_stress,
+    "hard_floats": sc_hard_floats,
 }

@@ -183,6 +183,10 @@ SCENARIOS = [
     # ranks agree on the table, and AUTO follows it to the right result)
     ("tune", 4, {"max_bytes": 65536}),
     ("tune", 7, {"max_bytes": 4096}),
+    # every rank-order form of allreduce / reduce on inputs where the fold order and special values show (tests/hard_inputs.py):
+    # the whole harness -- inputs, oracle, same_floats, the counters that confirm each form -- proven here before it sees a GPU
+    ("hard_floats", 3, None),
+    ("hard_floats", 8, None),
 ]
 
 
@@ -195,6 +199,7 @@ SCENARIOS += [
     ("bcast_reduce", 11, {"expect_params": {"dsync": 0}}),
     ("allgather", 12, {"counts": [0, 1, 1000, 4099, 65536 + 3], "expect_params": {"dsync": 0}}),
     ("helloworld", 16, {"expect_params": {"dsync": 0, "degraded": 0}}),
+    ("hard_floats", 9, {"expect_params": {"dsync": 0, "degraded": 0}}),
 ]
 
 

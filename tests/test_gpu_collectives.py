@@ -220,6 +220,27 @@ def test_split_form(size):
     run_ranks("split", size, timeout=600)
 
 
+@pytest.mark.parametrize("size", [2, 3, 8])
+def test_rank_order_forms_on_hard_floats(size):
+    """every rank-order form of allreduce and reduce -- AUTO, LL lines launched and by the agent, the one-kernel fold in both
+    unrolls, meet / body / done with either data kernel, push-only, DIRECT; the counters confirm each -- on inputs where another fold
+    order, a hardware minimum, a flushed subnormal or a touched NaN payload shows (tests/hard_inputs.py; sc_hard_floats), and the
+    copies byte for byte"""
+    run_ranks("hard_floats", size, timeout=300)
+
+
+def test_hard_floats_with_ranks_that_meet_on_the_host():
+    """the host rendezvous (one reduce_n_multi launch): processes under XMPI_DSYNC=0, then rank threads of one process"""
+    run_ranks("hard_floats", 3, {"expect_params": {"dsync": 0}}, timeout=300, env={"XMPI_DSYNC": "0"})
+    run_threads("hard_floats", 2)
+
+
+def test_hard_floats_through_the_staged_tables():
+    """XMPI_DSYNC=0 XMPI_ZERO_COPY=0: the DIRECT step tables (the reduce2_batch path)"""
+    run_ranks("hard_floats", 3, {"expect_staged": 1, "expect_params": {"dsync": 0, "zero_copy": 0}}, timeout=300,
+              env={"XMPI_DSYNC": "0", "XMPI_ZERO_COPY": "0"})
+
+
 @pytest.mark.parametrize("size,seed", [(2, 1), (3, 2), (5, 3), (8, 4)])
 def test_soak_every_form_mixed(size, seed):
     """a seeded random walk over every collective in every form, blocking and stream-ordered, with Send / Receive rings between

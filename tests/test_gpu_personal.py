@@ -50,6 +50,21 @@ def test_staged_tables(size):
               env={"XMPI_DSYNC": "0", "XMPI_ZERO_COPY": "0"})
 
 
+@pytest.mark.parametrize("size", [2, 3, 8])
+def test_reduce_scatter_on_hard_floats(size):
+    """reduce-scatter's rank-order fold where it can be seen -- dense mantissas, NaNs, infinities, signed zeros, subnormals
+    (tests/hard_inputs.py) -- by every name, one kernel and meet / body / done; all-to-all of the same data byte for byte"""
+    run_ranks("hard", size, timeout=240)
+
+
+def test_hard_floats_in_the_other_layouts():
+    """the host rendezvous (XMPI_DSYNC=0, and rank threads of one process) and the staged tables (XMPI_ZERO_COPY=0 as well)"""
+    run_ranks("hard", 3, {"expect_params": {"dsync": 0}}, timeout=240, env={"XMPI_DSYNC": "0"})
+    run_ranks("hard", 3, {"expect_staged": 1, "expect_params": {"dsync": 0, "zero_copy": 0}}, timeout=240,
+              env={"XMPI_DSYNC": "0", "XMPI_ZERO_COPY": "0"})
+    run_threads("hard", 2, timeout=240)
+
+
 def test_full_size():
     """8 ranks x 32 MiB per block, f32: the whole buffers compared on the device with an uploaded expectation"""
     run_ranks("fullsize", 8, timeout=300)

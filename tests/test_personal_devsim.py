@@ -82,6 +82,13 @@ def test_more_ranks_than_the_device_side_serves(size):
     run_ranks("layout", size, {"counts": [17, 4099], "expect_params": {"dsync": 0}}, timeout=300, env={"DEVSIM_DEVICES": "8"})
 
 
+@pytest.mark.parametrize("size", [3, 8, 9])
+def test_reduce_scatter_on_hard_floats(size):
+    """tests/hard_inputs.py data (full mantissas; NaNs, infinities, signed zeros, subnormals planted in every block) through
+    reduce-scatter by every name and form and through all-to-all; 9 ranks on 8 devices meet on the host"""
+    run_ranks("hard", size, {"expect_params": {"dsync": 0}} if size > 8 else None, timeout=300, env={"DEVSIM_DEVICES": "8"} if size > 8 else None)
+
+
 @pytest.mark.parametrize("size", [2, 3, 8])
 def test_ranks_in_different_calls_all_get_an_error(size):
     """an all-to-all against a reduce-scatter over the same bytes, above the LL limit: XMPI_ERR_ARG on every rank, nothing moved"""

@@ -48,6 +48,14 @@ size_t xmpi_sched_land_bytes(int sched, int in_place, int size, int rank, int ro
  * (16-byte aligned boundaries): element offset and length.  Host logic only. */
 int xmpi_zc_chunk(size_t count, size_t elem_size, int size, int j, size_t* elem_off, size_t* elem_cnt);
 
+/* The batch launchers of the staged step tables (mpi_amd/csrc/kernels.h launch_reduce2_batch / launch_copy_batch) on local
+ * buffers, n <= 16 segments in one call: dst[i] = a[i] op b[i] over counts[i] elements, resp. dst[i] = src[i] over bytes[i] bytes,
+ * and the same once more into dst2[i].  dst2 may be NULL or hold NULL entries; for the reduction dst[i] may be NULL as well (the
+ * result is only forwarded), and dst[i] may be a[i] or b[i] (dst2[i] then still holds the fold of the untouched operands). */
+int xmpi_reduce_local_batch(xmpi_comm* comm, void* const* dst, void* const* dst2, const void* const* a, const void* const* b,
+                            const size_t* counts, int n, xmpi_dtype dtype, xmpi_op op);
+int xmpi_copy_local_batch(xmpi_comm* comm, void* const* dst, void* const* dst2, const void* const* src, const size_t* bytes, int n);
+
 /* Host-only self-test of xmpi_malloc's block bookkeeping (no GPU call): `rounds` random allocate /
  * free operations on a synthetic arena; 0 = blocks never overlapped, stayed aligned and coalesced
  * back into one free block, otherwise the number of the failed check. */

@@ -981,6 +981,7 @@ long xmpi_get_param(const xmpi_comm* c, const char* name) {
   if (n == "zc_fallbacks_unmappable") return (long)c->zc_fallbacks_unmappable;
   if (n == "shared_stream") return c->shared_stream ? 1 : 0;
   if (n == "kernel_mode") return get_kernel_mode();
+  if (n == "grid_cap") return get_grid_cap();
   if (n == "last_run_us") return (long)c->last_run_us;
   if (n == "last_sync_us") return (long)c->last_sync_us;
   if (n == "lanes") return c->lanes;

@@ -11,7 +11,8 @@ constexpr int kMaxReduceSrcs = 16;
 
 // dst[i] = a[i] op b[i]; dst may alias a and/or b exactly (same address), never partially.
 // ev_start / ev_stop (optional, timing-enabled events): attached to the dispatch itself
-// (hipExtLaunchKernelGGL), i.e. they carry the kernel's own begin / end timestamps.
+// (hipExtLaunchKernelGGL), i.e. they carry the kernel's own begin / end timestamps.  Every launcher that takes them leaves
+// both RECORDED, also when it launches nothing (no elements, no destination): the caller reads the time between them.
 hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count, int dtype, int op,
                           hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // dst[i] = ((s0[i] op s1[i]) op s2[i]) ... left to right.
@@ -66,6 +67,7 @@ hipError_t launch_fill(void* buf, size_t count, int dtype, int pattern, uint64_t
 void set_kernel_mode(int mode);
 int get_kernel_mode();
 void set_grid_cap(int cap);
+int get_grid_cap();
 
 // ---- device-synchronised collectives (dsync.cpp) ------------------------------------------------
 // One kernel per rank IS the collective: it tells the peers (flag words in their HBM, written over xGMI)

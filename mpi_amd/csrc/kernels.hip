@@ -782,7 +782,6 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 template <typename T, int OP>
 hipError_t reduce2_typed(void* dst, const void* a, const void* b, size_t count, hipStream_t s, hipEvent_t es,
                          hipEvent_t ee) {
-  if (count == 0) return hipSuccess;
   if (aligned16(dst) && aligned16(a) && aligned16(b)) {
     constexpr size_t N = 16 / sizeof(T);
     const size_t npack = count / N;
@@ -860,6 +859,11 @@ hipError_t reduce_n_op(void* dst, const SrcPtrs& srcs, int nsrc, size_t count, i
 
 hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count, int dtype, int op,
                           hipStream_t s, hipEvent_t es, hipEvent_t ee) {
+  if (count == 0) {  // nothing to launch: still honour the events
+    if (es) (void)hipEventRecord(es, s);
+    if (ee) (void)hipEventRecord(ee, s);
+    return hipSuccess;
+  }
   switch (dtype) {
     case DT_U8: return reduce2_op<uint8_t>(dst, a, b, count, op, s, es, ee);
     case DT_I32: return reduce2_op<int32_t>(dst, a, b, count, op, s, es, ee);
@@ -875,7 +879,11 @@ hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count,
 hipError_t launch_reduce_n(void* dst, const void* const* srcs, int nsrc, size_t count, int dtype,
                            int op, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
   if (nsrc < 1 || nsrc > kMaxReduceSrcs) return hipErrorInvalidValue;
-  if (count == 0) return hipSuccess;
+  if (count == 0) {  // nothing to launch: still honour the events
+    if (es) (void)hipEventRecord(es, s);
+    if (ee) (void)hipEventRecord(ee, s);
+    return hipSuccess;
+  }
   if (nsrc == 1) {
     static const size_t esz[] = {1, 4, 8, 2, 4, 8, 2};
     if (dtype < 0 || dtype > DT_BF16) return hipErrorInvalidValue;
@@ -972,18 +980,22 @@ hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void*
   }
   if (!ok || (n == 1 && !fused) || maxc == 0) {  // odd alignment / nothing to fuse: plain launches
     // The local destination may alias an operand (in-place ring step: dst == a): the forwarded copy is
-    // computed FIRST, from the untouched operands, and the aliasing store comes last.
-    bool first = true;
+    // computed FIRST, from the untouched operands, and the aliasing store comes last.  The events ride on the first
+    // and the last launch there IS: a segment without elements or without a destination launches nothing.
+    int nlaunch = 0;
+    for (int i = 0; i < n; i++)
+      if (counts[i] > 0) nlaunch += (q.dst2[i] != nullptr) + (dst[i] != nullptr);
+    int k = 0;
     for (int i = 0; i < n; i++)
       for (int w = 0; w < 2; w++) {
         void* d = w == 0 ? q.dst2[i] : dst[i];
-        if (!d) continue;
-        const bool last = (i == n - 1) && (w == 1 || !dst[i]);
-        hipError_t e = launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, first ? es : nullptr, last ? ee : nullptr);
+        if (!d || counts[i] == 0) continue;
+        hipError_t e = launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, k == 0 ? es : nullptr,
+                                      k == nlaunch - 1 ? ee : nullptr);
         if (e != hipSuccess) return e;
-        first = false;
+        k++;
       }
-    if (maxc == 0) {  // nothing launched: still honour the events
+    if (nlaunch == 0) {  // nothing launched: still honour the events
       if (es) (void)hipEventRecord(es, s);
       if (ee) (void)hipEventRecord(ee, s);
     }
@@ -1017,17 +1029,24 @@ hipError_t launch_copy_batch(void* const* dst, void* const* dst2, const void* co
     fused = fused || b.dst2[i] != nullptr;
     ok = ok && aligned16(dst[i]) && aligned16(b.dst2[i]) && aligned16(src[i]);
   }
-  if (!ok || (n == 1 && !fused)) {  // odd alignment: one launch per copy, the events span the group
-    bool first = true;
+  if (!ok || (n == 1 && !fused)) {  // odd alignment: one launch per copy, the events span the group (as launch_reduce2_batch:
+    // on the first and the last launch there is)
+    int nlaunch = 0;
+    for (int i = 0; i < n; i++)
+      if (bytes[i] > 0) nlaunch += (dst[i] && dst[i] != src[i]) + (b.dst2[i] && b.dst2[i] != src[i]);
+    int k = 0;
     for (int i = 0; i < n; i++)
       for (int w = 0; w < 2; w++) {
         void* d = w == 0 ? dst[i] : b.dst2[i];
-        if (!d) continue;
-        const bool last = (i == n - 1) && (w == 1 || !b.dst2[i]);
-        hipError_t e = launch_copy(d, src[i], bytes[i], s, first ? es : nullptr, last ? ee : nullptr);
+        if (!d || d == src[i] || bytes[i] == 0) continue;
+        hipError_t e = launch_copy(d, src[i], bytes[i], s, k == 0 ? es : nullptr, k == nlaunch - 1 ? ee : nullptr);
         if (e != hipSuccess) return e;
-        first = false;
+        k++;
       }
+    if (nlaunch == 0) {  // nothing launched: still honour the events
+      if (es) (void)hipEventRecord(es, s);
+      if (ee) (void)hipEventRecord(ee, s);
+    }
     return hipSuccess;
   }
   if (maxb == 0) {
@@ -1236,6 +1255,7 @@ hipError_t launch_fill(void* buf, size_t count, int dtype, int pattern, uint64_t
 void set_kernel_mode(int mode) { g_kernel_mode = (mode < 0 || mode > 2) ? -1 : mode; }
 int get_kernel_mode() { return g_kernel_mode; }
 void set_grid_cap(int cap) { g_grid_cap = cap < 0 ? 0 : cap; }
+int get_grid_cap() { return g_grid_cap; }
 
 hipError_t launch_word_to_host(uint64_t* dst, const uint64_t* src, hipStream_t s) {
   hipLaunchKernelGGL(word_to_host_kernel, dim3(1), dim3(1), 0, s, dst, src);

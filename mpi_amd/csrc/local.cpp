@@ -111,6 +111,44 @@ int xmpi_copy_local_multi(xmpi_comm* c, void* const* dsts, int ndst, const void*
                       &ctx);
 }
 
+int xmpi_reduce_local_batch(xmpi_comm* c, void* const* dst, void* const* dst2, const void* const* a, const void* const* b,
+                            const size_t* counts, int n, xmpi_dtype dtype, xmpi_op op) {
+  XMPI_ENTER(c);
+  const size_t es = xmpi_dtype_size(dtype);
+  if (!es || op < 0 || op >= XMPI_OP_COUNT || n < 1 || n > kMaxBatch || !dst || !a || !b || !counts) return XMPI_ERR_ARG;
+  size_t total = 0;
+  for (int i = 0; i < n; i++) {
+    if (!a[i] || !b[i]) return XMPI_ERR_ARG;  // (dst[i] and dst2[i] may be null: kernels.h)
+    total += counts[i];
+  }
+  struct Ctx { xmpi_comm* c; void* const* d; void* const* d2; const void* const* a; const void* const* b; const size_t* n; int segs, dt, op; }
+      ctx{c, dst, dst2, a, b, counts, n, (int)dtype, (int)op};
+  return timed_launch(c, PROF_REDUCE2, 3 * total * es,
+                      [](void* p, hipEvent_t es, hipEvent_t ee) {
+                        Ctx* x = (Ctx*)p;
+                        return launch_reduce2_batch(x->d, x->d2, x->a, x->b, x->n, x->segs, x->dt, x->op, x->c->local_stream,
+                                                    es, ee);
+                      },
+                      &ctx);
+}
+
+int xmpi_copy_local_batch(xmpi_comm* c, void* const* dst, void* const* dst2, const void* const* src, const size_t* bytes, int n) {
+  XMPI_ENTER(c);
+  if (n < 1 || n > kMaxBatch || !dst || !src || !bytes) return XMPI_ERR_ARG;
+  size_t total = 0;
+  for (int i = 0; i < n; i++) {
+    if (!dst[i] || !src[i]) return XMPI_ERR_ARG;  // (only dst2[i] may be null: kernels.h)
+    total += bytes[i];
+  }
+  struct Ctx { xmpi_comm* c; void* const* d; void* const* d2; const void* const* s; const size_t* n; int segs; } ctx{c, dst, dst2, src, bytes, n};
+  return timed_launch(c, PROF_COPY, 2 * total,
+                      [](void* p, hipEvent_t es, hipEvent_t ee) {
+                        Ctx* x = (Ctx*)p;
+                        return launch_copy_batch(x->d, x->d2, x->s, x->n, x->segs, x->c->local_stream, es, ee);
+                      },
+                      &ctx);
+}
+
 int xmpi_count_mismatch(xmpi_comm* c, const void* a, const void* b, size_t bytes, uint64_t* out) {
   XMPI_ENTER(c);
   if (!out) return XMPI_ERR_ARG;

@@ -89,6 +89,8 @@ SYMBOLS = [
     ("xmpi_reduce_local_multi", _I, [_P, C.POINTER(_P), _I, C.POINTER(_P), _I, _Z, _I, _I]),
     ("xmpi_copy_local_multi", _I, [_P, C.POINTER(_P), _I, _P, _Z]),
     ("xmpi_copy_local_pairs", _I, [_P, C.POINTER(_P), C.POINTER(_P), _I, _Z]),
+    ("xmpi_reduce_local_batch", _I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z), _I, _I, _I]),
+    ("xmpi_copy_local_batch", _I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z), _I]),
     ("xmpi_zc_chunk", _I, [_Z, _Z, _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),
     ("xmpi_allreduce_on_stream", _I, [_P, _P, _P, _Z, _I, _I, _P]),
     ("xmpi_allgather_on_stream", _I, [_P, _P, _P, _Z, _I, _P]),
@@ -439,6 +441,23 @@ class Comm:
     def copy_local_multi(self, dsts: Sequence, src, nbytes: int) -> None:
         d = (_P * len(dsts))(*[_ptr(x) for x in dsts])
         _check(lib().xmpi_copy_local_multi(self.handle, d, len(dsts), _ptr(src), nbytes), "copy_local_multi")
+
+    def reduce_local_batch(self, dsts: Sequence, dsts2: Optional[Sequence], a: Sequence, b: Sequence, counts: Sequence[int], dtype: int,
+                           op: int = SUM) -> None:
+        """dsts[i] = a[i] op b[i] over counts[i] elements, every segment in one call (the staged tables' batch launcher); the same
+        into dsts2[i]; None entries of dsts / dsts2 (and dsts2 = None) are destinations that are not there"""
+        n = len(a)
+        d = (_P * n)(*[_ptr(x) for x in dsts])
+        d2 = (_P * n)(*[_ptr(x) for x in dsts2]) if dsts2 is not None else None
+        pa, pb = (_P * n)(*[_ptr(x) for x in a]), (_P * n)(*[_ptr(x) for x in b])
+        _check(lib().xmpi_reduce_local_batch(self.handle, d, d2, pa, pb, (_Z * n)(*counts), n, dtype, op), "reduce_local_batch")
+
+    def copy_local_batch(self, dsts: Sequence, dsts2: Optional[Sequence], srcs: Sequence, nbytes: Sequence[int]) -> None:
+        """dsts[i] = srcs[i] over nbytes[i] bytes, every copy in one call; the same into dsts2[i] where it is not None"""
+        n = len(srcs)
+        d = (_P * n)(*[_ptr(x) for x in dsts])
+        d2 = (_P * n)(*[_ptr(x) for x in dsts2]) if dsts2 is not None else None
+        _check(lib().xmpi_copy_local_batch(self.handle, d, d2, (_P * n)(*[_ptr(x) for x in srcs]), (_Z * n)(*nbytes), n), "copy_local_batch")
 
     def register(self, ptr, nbytes: int) -> None:
         """Make device memory that did not come from alloc() reachable by the zero-copy collectives."""

@@ -3288,6 +3288,530 @@ def hard_stepped(comm, counts):
     sums.free()
 
 
+# ---- every cache-policy variant and every capped grid of the streaming kernels -------------------------------------------------------
+# kernels.hip compiles each streaming kernel once per cache policy (MODE 0 plain, 1 non-temporal loads and stores, 2 non-temporal
+# loads) and picks by traffic: below 48 MiB -- every other test shape -- MODE 0.  The grid-stride loops go round more than once only
+# under a grid cap.  Both are process-wide knobs ("kernel_mode", "grid_cap"): sc_kernel_variants walks all nine pairs.
+KV_VARIANTS = [(mode, cap) for mode in (0, 1, 2) for cap in (0, 1, 3)]
+# counts are npack * N + tail, N = 16 / element size, tail = N - 1 (u8: 0).  In packets, the smallest sizes at which a loop or a
+# branch changes -- none, one lane, one short of / exactly / one past a tile (1024 packets: reduce2, copy16, copy_multi, the batch
+# kernels) resp. a block (256 packets, one per lane: reduce_n, reduce_n_multi, copy_pairs), three of them (cap 3: one sweep), one
+# more (a block's second tile is the partial one), and seven and a bit (cap 3: two full tiles, a full and a partial one, none)
+KV_TILE = [0, 1, 1023, 1024, 1025, 3072, 3073, 7 * 1024 + 300]
+KV_LANE = [0, 1, 255, 256, 257, 768, 769, 7 * 256 + 100]
+KV_FULL = [(xmpi.F32, xmpi.SUM), (xmpi.F16, xmpi.PROD), (xmpi.BF16, xmpi.MAX), (xmpi.U8, xmpi.SUM)]  # these walk the whole list ...
+KV_DTYPES = (xmpi.U8, xmpi.I32, xmpi.I64, xmpi.F16, xmpi.F32, xmpi.F64, xmpi.BF16)                  # ... every dtype x operator runs
+KV_OPS = (xmpi.SUM, xmpi.PROD, xmpi.MIN, xmpi.MAX)                                                  # the 3073 / 769 shape
+
+
+def kv_count(dtype, npack):
+    n = 16 // xmpi.DTYPE_SIZE[dtype]
+    return npack * n + (0 if dtype == xmpi.U8 else n - 1)
+
+
+def kv_shapes(npacks):
+    """(dtype, operation, elements, elements every buffer starts into its allocation): the whole list and one unaligned case -- the
+    element kernels, which have no MODE -- for KV_FULL, the one-past-three-tiles shape for everything else"""
+    out = []
+    for dtype in KV_DTYPES:
+        for op in KV_OPS:
+            if (dtype, op) in KV_FULL:
+                out += [(dtype, op, kv_count(dtype, p), 0) for p in npacks] + [(dtype, op, kv_count(dtype, npacks[4]), 1)]
+            else:
+                out.append((dtype, op, kv_count(dtype, npacks[6]), 0))
+    return out
+
+
+def kv_kinds(dtype, op):
+    """floats: tests/hard_inputs.py -- dense (full mantissas: bit for bit) and special (under same_floats; a product's data is
+    dense(spread 1) either way); integers: PAT_UNIFORM"""
+    return ("integer",) if dtype not in FLOATS else ("dense",) if op == xmpi.PROD else ("dense", "special")
+
+
+def kv_inputs(dtype, op, count, kind, nsrc=2, seed=0):
+    """(the operands, the CPU oracle's left-to-right fold of them)"""
+    if count == 0:
+        e = np.empty(0, dtype=xmpi.NUMPY_DTYPE[dtype])
+        return [e] * nsrc, e
+    if kind == "integer":
+        ins = [oracle.fill(count, dtype, xmpi.PAT_UNIFORM, 900 + seed + r) for r in range(nsrc)]
+        return ins, oracle.reduce_ranks(ins, dtype, op)
+    return hard_case(dtype, count, (7200 if kind == "dense" else 7000) + seed, nsrc, op, kind)
+
+
+def kv_check(kind, got: bytes, want, dtype, op, what):
+    if kind == "special":
+        hi.same_floats(np.frombuffer(got, dtype=xmpi.NUMPY_DTYPE[dtype]), want, dtype, op, what)
+    elif got != want.tobytes():
+        g, w = np.frombuffer(got, dtype=np.uint8), np.frombuffer(want.tobytes(), dtype=np.uint8)
+        assert g.size == w.size, f"{what}: {g.size} bytes, expected {w.size}"
+        bad = np.nonzero(g != w)[0]
+        raise AssertionError(f"{what}: {bad.size} of {g.size} bytes differ from the oracle, the first at byte {int(bad[0])}")
+
+
+class KvArena:
+    """Buffers side by side in one allocation, each with 16 guard bytes of 0xEE on either side (and `shift` bytes into its frame: the
+    unaligned cases): one memset arms all of them, one download reads all of them and checks every byte that is nobody's data."""
+
+    def __init__(self, comm, spans):  # spans: (bytes, shift) per buffer
+        self.comm, self.spans, self.off, self.frame = comm, list(spans), [], []
+        pos = 0
+        for nb, shift in self.spans:
+            size = 32 + (shift + nb + 15) // 16 * 16
+            self.frame.append((pos, size))
+            self.off.append(pos + 16 + shift)
+            pos += size
+        self.total = pos
+        self.buf = comm.alloc(pos)
+        self.is_data = np.zeros(pos, dtype=bool)
+        for (nb, _), o in zip(self.spans, self.off):
+            self.is_data[o:o + nb] = True
+        self.reset()
+
+    def reset(self):
+        self.comm.memset(self.buf, 0xEE, self.total)
+
+    def ptr(self, k):
+        return self.buf.at(self.off[k])
+
+    def put(self, k, arr):
+        assert arr.nbytes == self.spans[k][0]
+        self.buf.upload(arr, byte_offset=self.off[k])
+
+    def get(self, what):
+        """every buffer's bytes; whatever lies between them is still 0xEE"""
+        whole = self.buf.download(np.uint8, self.total)
+        assert np.all(whole[~self.is_data] == 0xEE), f"{what}: a guard byte round a buffer was written"
+        return [whole[o:o + nb].tobytes() for (nb, _), o in zip(self.spans, self.off)]
+
+    def get_one(self, k, what):
+        pos, size = self.frame[k]
+        frame = self.buf.download(np.uint8, size, byte_offset=pos)
+        lo, nb = self.off[k] - pos, self.spans[k][0]
+        assert np.all(frame[:lo] == 0xEE) and np.all(frame[lo + nb:] == 0xEE), f"{what}: a guard byte round buffer {k} was written"
+        return frame[lo:lo + nb].tobytes()
+
+    def free(self):
+        self.buf.free()
+
+
+class KvRun:
+    def __init__(self, comm):
+        self.comm, self.launches, self.cases = comm, 0, 0
+        self.special = {}  # kernel -> [cases of special data in which the variants' bytes differ, elements that differ]
+
+    def variants(self):
+        for mode, cap in KV_VARIANTS:
+            self.comm.set_param("kernel_mode", mode)
+            self.comm.set_param("grid_cap", cap)
+            got = (self.comm.get_param("kernel_mode"), self.comm.get_param("grid_cap"))
+            assert got == (mode, cap), f"kernel_mode, grid_cap read back as {got} after {(mode, cap)} was set"
+            yield f"kernel_mode={mode} grid_cap={cap}"
+
+    def same(self, kernel, kind, dtype, results, what):
+        """dense and integer data: all nine variants return the same bytes.  Special data: reported, not asserted -- which of two
+        NaNs' payloads a SUM returns is settled per instantiation"""
+        self.cases += 1
+        for v, r in zip(KV_VARIANTS[1:], results[1:]):
+            if r == results[0]:
+                continue
+            assert kind == "special", f"{what}: kernel_mode, grid_cap = {v} returns other bytes than {KV_VARIANTS[0]}"
+            es = xmpi.DTYPE_SIZE[dtype]
+            a, b = (np.frombuffer(x, dtype=np.uint8).reshape(-1, es) for x in (results[0], r))
+            key = f"{kernel} {xmpi.DTYPE_NAME[dtype]}"  # (each passed same_floats: what differs is a NaN in both, and the operation SUM)
+            self.special.setdefault(key, [0, 0])
+            self.special[key][0] += 1
+            self.special[key][1] += int(np.sum(np.any(a != b, axis=1)))
+            break
+
+
+def kv_reduce2(run):
+    """reduce_local: out of place, and with the destination on the first operand"""
+    comm = run.comm
+    for dtype, op, count, shift in kv_shapes(KV_TILE):
+        es = xmpi.DTYPE_SIZE[dtype]
+        span = (count * es, shift * es)
+        for kind in kv_kinds(dtype, op):
+            ins, want = kv_inputs(dtype, op, count, kind)
+            src, dst = KvArena(comm, [span] * 2), KvArena(comm, [span])
+            for k in range(2):
+                src.put(k, ins[k])
+            results = []
+            for v in run.variants():
+                what = f"reduce_local {xmpi.DTYPE_NAME[dtype]} op={op} n={count} shift={shift} {kind} data, {v}"
+                dst.reset()
+                comm.reduce_local(dst.ptr(0), src.ptr(0), src.ptr(1), count, dtype, op)
+                out = dst.get(what)[0]
+                kv_check(kind, out, want, dtype, op, what)
+                comm.reduce_local(src.ptr(0), src.ptr(0), src.ptr(1), count, dtype, op)
+                inplace = src.get_one(0, what + ", in place")
+                kv_check(kind, inplace, want, dtype, op, what + ", in place")
+                src.put(0, ins[0])
+                results.append(out + inplace)
+                run.launches += 2
+            assert src.get(what) == [x.tobytes() for x in ins], f"{what}: a source was modified"
+            run.same("reduce2", kind, dtype, results, what)
+            src.free()
+            dst.free()
+
+
+def kv_reduce_n(run, nsrcs):
+    """reduce_local_n (nsrc 9 and 16: the generic instantiation): out of place, and with the destination on the first source"""
+    comm = run.comm
+    for nsrc in nsrcs:
+        for dtype, op, count, shift in kv_shapes(KV_LANE):
+            es = xmpi.DTYPE_SIZE[dtype]
+            span = (count * es, shift * es)
+            for kind in kv_kinds(dtype, op):
+                ins, want = kv_inputs(dtype, op, count, kind, nsrc)
+                src, dst = KvArena(comm, [span] * nsrc), KvArena(comm, [span])
+                for k in range(nsrc):
+                    src.put(k, ins[k])
+                srcs = [src.ptr(k) for k in range(nsrc)]
+                results = []
+                for v in run.variants():
+                    what = f"reduce_local_n nsrc={nsrc} {xmpi.DTYPE_NAME[dtype]} op={op} n={count} shift={shift} {kind} data, {v}"
+                    dst.reset()
+                    comm.reduce_local_n(dst.ptr(0), srcs, count, dtype, op)
+                    out = dst.get(what)[0]
+                    kv_check(kind, out, want, dtype, op, what)
+                    comm.reduce_local_n(srcs[0], srcs, count, dtype, op)
+                    inplace = src.get_one(0, what + ", in place")
+                    kv_check(kind, inplace, want, dtype, op, what + ", in place")
+                    src.put(0, ins[0])
+                    results.append(out + inplace)
+                    run.launches += 2
+                assert src.get(what) == [x.tobytes() for x in ins], f"{what}: a source was modified"
+                run.same(f"reduce_n<{nsrc if nsrc <= 8 else 'generic'}>", kind, dtype, results, what)
+                src.free()
+                dst.free()
+
+
+def kv_multi(run, pairs):
+    """reduce_local_multi: every destination fresh, then the last one on a source (in place under non-temporal stores)"""
+    comm = run.comm
+    for nsrc, ndst in pairs:
+        alias = min(1, nsrc - 1)
+        for dtype, op, count, shift in kv_shapes(KV_LANE):
+            es = xmpi.DTYPE_SIZE[dtype]
+            span = (count * es, shift * es)
+            for kind in kv_kinds(dtype, op):
+                ins, want = kv_inputs(dtype, op, count, kind, nsrc)
+                src, dst = KvArena(comm, [span] * nsrc), KvArena(comm, [span] * ndst)
+                for k in range(nsrc):
+                    src.put(k, ins[k])
+                srcs = [src.ptr(k) for k in range(nsrc)]
+                untouched = b"\xEE" * span[0]
+                results = []
+                for v in run.variants():
+                    what = f"reduce_local_multi nsrc={nsrc} ndst={ndst} {xmpi.DTYPE_NAME[dtype]} op={op} n={count} shift={shift} {kind} data, {v}"
+                    dst.reset()
+                    comm.reduce_local_multi([dst.ptr(k) for k in range(ndst)], srcs, count, dtype, op)
+                    outs = dst.get(what)
+                    kv_check(kind, outs[0], want, dtype, op, what)
+                    assert all(o == outs[0] for o in outs), f"{what}: the destinations differ from each other"
+                    dst.reset()
+                    comm.reduce_local_multi([dst.ptr(k) for k in range(ndst - 1)] + [srcs[alias]], srcs, count, dtype, op)
+                    outs2 = dst.get(what + ", last destination on a source")
+                    inplace = src.get_one(alias, what + ", last destination on a source")
+                    kv_check(kind, inplace, want, dtype, op, what + ", last destination on a source")
+                    assert all(o == inplace for o in outs2[:ndst - 1]) and outs2[ndst - 1] == untouched, \
+                        f"{what}, last destination on a source: the destinations differ from each other, or one that was not named was written"
+                    src.put(alias, ins[alias])
+                    results.append(outs[0] + inplace)
+                    run.launches += 2
+                assert src.get(what) == [x.tobytes() for x in ins], f"{what}: a source was modified"
+                run.same(f"reduce_n_multi<{nsrc if nsrc <= 8 else 'generic'}>", kind, dtype, results, what)
+                src.free()
+                dst.free()
+
+
+def kv_copy(run):
+    """copy_local, copy_local_multi (1, 7, 15 destinations; the source listed too: skipped), copy_local_pairs (1, 3, 8, 9 pairs; 9:
+    the generic instantiation): bytes with and without a tail, and copy / copy_multi one byte into every buffer (the byte kernels)"""
+    comm = run.comm
+
+    def sizes(npacks, unaligned):
+        return [(p * 16 + t, 0) for p in npacks for t in (0, 15)] + ([(npacks[4] * 16 + 15, 1)] if unaligned else [])
+
+    def case(name, nsrc, ndst, spans, call):
+        nb = spans[0]
+        ins = [oracle.fill(nb, xmpi.U8, xmpi.PAT_UNIFORM, 40 + k) for k in range(nsrc)]
+        src, dst = KvArena(comm, [spans] * nsrc), KvArena(comm, [spans] * ndst)
+        for k in range(nsrc):
+            src.put(k, ins[k])
+        results = []
+        for v in run.variants():
+            what = f"{name} {nb} bytes shift={spans[1]}, {v}"
+            dst.reset()
+            call(src, dst, nb)
+            outs = dst.get(what)
+            for k, o in enumerate(outs):
+                assert o == ins[k % nsrc].tobytes(), f"{what}: destination {k} differs from its source"
+            results.append(b"".join(outs))
+            run.launches += 1
+        assert src.get(what) == [x.tobytes() for x in ins], f"{what}: a source was modified"
+        run.same(name, "integer", xmpi.U8, results, what)
+        src.free()
+        dst.free()
+
+    for spans in sizes(KV_TILE, True):
+        case("copy_local", 1, 1, spans, lambda s, d, nb: comm.copy_local(d.ptr(0), s.ptr(0), nb))
+        for ndst in (1, 7, 15):
+            case(f"copy_local_multi ndst={ndst}", 1, ndst, spans,
+                 lambda s, d, nb, ndst=ndst: comm.copy_local_multi([d.ptr(k) for k in range(ndst)] + [s.ptr(0)], s.ptr(0), nb))
+    for spans in sizes(KV_LANE, False):
+        for n in (1, 3, 8, 9):
+            case(f"copy_local_pairs n={n}", n, n, spans,
+                 lambda s, d, nb, n=n: comm.copy_local_pairs([d.ptr(k) for k in range(n)], [s.ptr(k) for k in range(n)], nb))
+
+
+# The batch launchers' contract (kernels.h): segments of unequal and of no length in one launch; dst null (the result is only
+# forwarded); dst2 per segment, null, or no dst2 array at all; dst on operand a with dst2 elsewhere -- the in-place ring step --
+# aligned and with one pointer one element off (the fallback: dst2 must be computed from the untouched operands).
+# (name, per segment (packets, None = no elements; dst: "own" / None / "a"; dst2: "own" / None), a dst2 array is passed,
+# (segment, pointer) that lies one element into its buffer)
+_O, _A = "own", "a"
+KV_BATCH = [
+    ("n=1, nothing to fuse", [(3073, _O, None)], False, None),
+    ("n=1, two destinations", [(1025, _O, _O)], True, None),
+    ("n=2, forwarded only + both", [(1024, None, _O), (3072, _O, _O)], True, None),
+    ("n=2, no dst2 array", [(1025, _O, None), (1, _O, None)], False, None),
+    ("n=5, unequal and empty segments", [(1, _O, None), (None, _O, _O), (1023, None, _O), (7 * 1024 + 300, _O, _O), (None, _O, None)], True, None),
+    ("n=5, unequal and empty segments, unaligned", [(1, _O, None), (None, _O, _O), (1023, None, _O), (7 * 1024 + 300, _O, _O), (None, _O, None)], True, (3, "dst2")),
+    ("n=16", [(p, *((_O, _O), (None, _O), (_O, None))[i % 3]) for i, p in
+              enumerate([0, 1, 1023, 1024, 1025, 3072, 3073, 300, 1, 1024, None, 1025, 2, 1023, 3073, None])], True, None),
+    ("in-place ring step", [(3073, _A, _O), (1025, _A, _O)], True, None),
+    ("in-place ring step, unaligned", [(3073, _A, _O), (1025, _A, _O)], True, (1, "b")),
+]
+
+
+def kv_batch_reduce(run):
+    comm = run.comm
+    for name, segs, with_dst2, odd in KV_BATCH:
+        n = len(segs)
+        for dtype in KV_DTYPES:
+            for op in KV_OPS:
+                if (dtype, op) not in KV_FULL and name != "n=16":
+                    continue
+                es = xmpi.DTYPE_SIZE[dtype]
+                counts = [0 if p is None else kv_count(dtype, p) for p, _, _ in segs]
+                shift = lambda i, which: es if odd == (i, which) else 0
+                for kind in kv_kinds(dtype, op):
+                    data = [kv_inputs(dtype, op, c, kind, seed=16 * i) for i, c in enumerate(counts)]
+                    src = KvArena(comm, [(c * es, shift(i, w)) for i, c in enumerate(counts) for w in ("a", "b")])
+                    dst = KvArena(comm, [(c * es, shift(i, w)) for i, c in enumerate(counts) for w in ("dst", "dst2")])
+                    for i, (ins, _) in enumerate(data):
+                        src.put(2 * i, ins[0])
+                        src.put(2 * i + 1, ins[1])
+                    a, b = [src.ptr(2 * i) for i in range(n)], [src.ptr(2 * i + 1) for i in range(n)]
+                    d = [dst.ptr(2 * i) if k == _O else a[i] if k == _A else None for i, (_, k, _) in enumerate(segs)]
+                    d2 = [dst.ptr(2 * i + 1) if k == _O else None for i, (_, _, k) in enumerate(segs)] if with_dst2 else None
+                    results = []
+                    for v in run.variants():
+                        what = f"reduce_local_batch [{name}] {xmpi.DTYPE_NAME[dtype]} op={op} counts={counts} {kind} data, {v}"
+                        dst.reset()
+                        comm.reduce_local_batch(d, d2, a, b, counts, dtype, op)
+                        outs, ops = dst.get(what), src.get(what)
+                        got = b""
+                        for i, (_, kd, kd2) in enumerate(segs):
+                            ins, want = data[i]
+                            untouched = b"\xEE" * (counts[i] * es)
+                            for slot, there, which in ((2 * i + 1, with_dst2 and kd2 == _O, "dst2"), (2 * i, kd == _O, "dst")):
+                                if there:
+                                    kv_check(kind, outs[slot], want, dtype, op, f"{what}: {which} of segment {i}")
+                                    got += outs[slot]
+                                else:
+                                    assert outs[slot] == untouched, f"{what}: segment {i} has no {which}, and the buffer standing in for it was written"
+                            if kd == _A:
+                                kv_check(kind, ops[2 * i], want, dtype, op, f"{what}: segment {i}, dst on operand a")
+                                got += ops[2 * i]
+                                src.put(2 * i, ins[0])
+                            else:
+                                assert ops[2 * i] == ins[0].tobytes(), f"{what}: operand a of segment {i} was modified"
+                            assert ops[2 * i + 1] == ins[1].tobytes(), f"{what}: operand b of segment {i} was modified"
+                        results.append(got)
+                        run.launches += 1
+                    run.same("reduce2_batch" + (" (fallback)" if odd or (n == 1 and not with_dst2) else ""), kind, dtype, results, what)
+                    src.free()
+                    dst.free()
+
+
+def kv_batch_copy(run):
+    comm = run.comm
+    for name, segs, with_dst2, odd in KV_BATCH:
+        if any(kd == _A for _, kd, _ in segs):
+            continue  # (a copy onto its own source is nothing)
+        n = len(segs)
+        nbytes = [0 if p is None else p * 16 + 15 for p, _, _ in segs]
+        shift = lambda i, which: 1 if odd == (i, which) else 0
+        ins = [oracle.fill(nb, xmpi.U8, xmpi.PAT_UNIFORM, 60 + i) for i, nb in enumerate(nbytes)]
+        src = KvArena(comm, [(nb, 0) for nb in nbytes])
+        dst = KvArena(comm, [(nb, shift(i, w)) for i, nb in enumerate(nbytes) for w in ("dst", "dst2")])
+        for i, x in enumerate(ins):
+            src.put(i, x)
+        s = [src.ptr(i) for i in range(n)]
+        d = [dst.ptr(2 * i) for i in range(n)]  # (a copy always has its first destination)
+        d2 = [dst.ptr(2 * i + 1) if k == _O else None for i, (_, _, k) in enumerate(segs)] if with_dst2 else None
+        results = []
+        for v in run.variants():
+            what = f"copy_local_batch [{name}] bytes={nbytes}, {v}"
+            dst.reset()
+            comm.copy_local_batch(d, d2, s, nbytes)
+            outs = dst.get(what)
+            for i, (_, _, kd2) in enumerate(segs):
+                assert outs[2 * i] == ins[i].tobytes(), f"{what}: dst of segment {i} differs from its source"
+                assert outs[2 * i + 1] == (ins[i].tobytes() if with_dst2 and kd2 == _O else b"\xEE" * nbytes[i]), \
+                    f"{what}: dst2 of segment {i} differs from its source, or is not there and was written"
+            results.append(b"".join(outs))
+            run.launches += 1
+        assert src.get(what) == [x.tobytes() for x in ins], f"{what}: a source was modified"
+        run.same("copy_batch" + (" (fallback)" if odd or (n == 1 and not with_dst2) else ""), "integer", xmpi.U8, results, what)
+        src.free()
+        dst.free()
+
+
+def kv_verify(run):
+    """fill, count_mismatch, checksum and diff_stats go through the same grid rule: under the caps their loops go round too"""
+    comm = run.comm
+    n = 5 * 1024 + 7  # (fill: 4 elements per lane, 6 blocks)
+    nb = (7 * 1024 + 300) * 16 + 15
+    a = oracle.fill(nb + 8, xmpi.U8, xmpi.PAT_UNIFORM, 5)
+    b = a.copy()
+    for i in (0, 1, 17, 4096, 4097, 16 * 1024 - 1, 16 * 1024, 48 * 1024 + 5, nb // 2, nb - 1, nb + 7):
+        b[i] ^= 0x40
+    da, db = comm.alloc(nb + 8).upload(a), comm.alloc(nb + 8).upload(b)
+    nd = 5 * 2048 + 77  # (diff_stats: 8 elements per lane, 6 blocks)
+    for v in run.variants():
+        for dtype in KV_DTYPES:
+            es = xmpi.DTYPE_SIZE[dtype]
+            buf = KvArena(comm, [(n * es, 0)])
+            for pattern in (xmpi.PAT_UNIFORM, xmpi.PAT_INDEX, xmpi.PAT_CONST, xmpi.PAT_SIGNED):
+                buf.reset()
+                comm.fill(buf.ptr(0), n, dtype, pattern, 12345)
+                what = f"fill {xmpi.DTYPE_NAME[dtype]} pattern {pattern} n={n}, {v}"
+                assert buf.get(what)[0] == oracle.fill(n, dtype, pattern, 12345).tobytes(), f"{what}: differs from the oracle"
+                run.launches += 1
+            buf.free()
+        for off, length in ((0, nb), (0, nb + 8), (1, nb), (3, nb - 3), (16, 1023 * 16)):
+            what = f"bytes [{off}, {off + length}), {v}"
+            assert comm.count_mismatch(da.at(off), db.at(off), length) == oracle.count_mismatch(a[off:off + length], b[off:off + length]) > 0, f"count_mismatch {what}"
+            assert comm.count_mismatch(da.at(off), da.at(off), length) == 0, f"count_mismatch of a buffer with itself, {what}"
+            assert comm.checksum(da.at(off), length) == oracle.checksum(a[off:off + length]), f"checksum {what}"
+            assert comm.checksum(db.at(off), length) == oracle.checksum(b[off:off + length]), f"checksum {what}"
+            run.launches += 4
+        for dtype in FLOATS:
+            # PAT_INDEX: multiples of 2^-8 (f16: 2^-6, bf16: 2^-4) below 256 -- max |x - y| and sum |y| over 10317 elements are exact
+            # in a double in ANY association, so the block and atomic sums must give the oracle's very numbers at every grid
+            x, y = oracle.fill(nd, dtype, xmpi.PAT_INDEX, 1), oracle.fill(nd, dtype, xmpi.PAT_INDEX, 2)
+            es = xmpi.DTYPE_SIZE[dtype]
+            dx, dy = comm.alloc(nd * es).upload(x), comm.alloc(nd * es).upload(y)
+            assert comm.diff_stats(dx, dy, nd, dtype) == oracle.diff_stats(x, y, dtype), f"diff_stats {xmpi.DTYPE_NAME[dtype]}, {v}"
+            run.launches += 1
+            dx.free()
+            dy.free()
+    da.free()
+    db.free()
+
+
+def kv_profile(run):
+    """With profiling on every local entry carries a begin and an end event into its launcher and reads the time between them
+    afterwards: a launcher that returns early -- no elements, no destination -- must still have recorded both.  Each call returns OK
+    (the binding raises otherwise), prof_get counts it, its bytes are the entry's own formula, and a call that launched nothing adds
+    less than a millisecond"""
+    comm = run.comm
+    comm.prof_enable(True)
+    dtype, es, op = xmpi.F32, 4, xmpi.SUM
+    (x, y, z), _ = kv_inputs(dtype, op, 17, "dense", 3)
+    src = KvArena(comm, [(17 * es, 0)] * 3 + [(17 * es, es)])  # (3: operand y once more, one element into its buffer)
+    for k, arr in enumerate((x, y, z, y)):
+        src.put(k, arr)
+    dst = KvArena(comm, [(17 * es, 0)] * 4)
+    want2, want3 = oracle.reduce2(x, y, dtype, op).tobytes(), oracle.reduce_ranks([x, y, z], dtype, op).tobytes()
+    X, Y, Z, Yodd = (src.ptr(k) for k in range(4))
+    D = [dst.ptr(k) for k in range(4)]
+    calls = [
+        # (what, profile counter, the call, elements or bytes the entry accounts for per its formula, expected buffers (None: untouched))
+        ("reduce_local of no elements", xmpi.PROF_REDUCE2, lambda: comm.reduce_local(D[0], X, Y, 0, dtype, op), 0, [None] * 4),
+        ("reduce_local of 17", xmpi.PROF_REDUCE2, lambda: comm.reduce_local(D[0], X, Y, 17, dtype, op), 3 * 17 * es, [want2, None, None, None]),
+        ("reduce_local_n of no elements", xmpi.PROF_REDUCEN, lambda: comm.reduce_local_n(D[0], [X, Y, Z], 0, dtype, op), 0, [None] * 4),
+        ("reduce_local_n of 17", xmpi.PROF_REDUCEN, lambda: comm.reduce_local_n(D[0], [X, Y, Z], 17, dtype, op), 4 * 17 * es, [want3, None, None, None]),
+        ("reduce_local_n of one source and no elements", xmpi.PROF_REDUCEN, lambda: comm.reduce_local_n(D[0], [X], 0, dtype, op), 0, [None] * 4),
+        ("reduce_local_batch, last segment empty", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], D[2]], [D[1], D[3]], [X, X], [Y, Y], [17, 0], dtype, op), 3 * 17 * es, [want2, want2, None, None]),
+        ("reduce_local_batch, unaligned, last segment empty", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], D[2]], [D[1], D[3]], [X, X], [Yodd, Y], [17, 0], dtype, op), 3 * 17 * es, [want2, want2, None, None]),
+        ("reduce_local_batch, unaligned, first segment empty", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], D[2]], [D[1], D[3]], [X, X], [Y, Yodd], [0, 17], dtype, op), 3 * 17 * es, [None, None, want2, want2]),
+        ("reduce_local_batch, unaligned, last segment without a destination", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], None], [D[1], None], [X, X], [Yodd, Y], [17, 17], dtype, op), 3 * 34 * es, [want2, want2, None, None]),
+        ("reduce_local_batch of no elements", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], D[2]], [D[1], D[3]], [X, X], [Y, Y], [0, 0], dtype, op), 0, [None] * 4),
+        ("reduce_local_batch of no elements, unaligned", xmpi.PROF_REDUCE2,
+         lambda: comm.reduce_local_batch([D[0], D[2]], [D[1], D[3]], [X, X], [Yodd, Y], [0, 0], dtype, op), 0, [None] * 4),
+        ("copy_local_batch, last segment empty", xmpi.PROF_COPY,
+         lambda: comm.copy_local_batch([D[0], D[2]], [D[1], D[3]], [X, Y], [17 * es, 0]), 2 * 17 * es, [x.tobytes(), x.tobytes(), None, None]),
+        ("copy_local_batch, unaligned, last segment empty", xmpi.PROF_COPY,
+         lambda: comm.copy_local_batch([D[0], D[2]], [D[1], D[3]], [Yodd, X], [17 * es, 0]), 2 * 17 * es, [y.tobytes(), y.tobytes(), None, None]),
+        ("copy_local_batch of no bytes", xmpi.PROF_COPY, lambda: comm.copy_local_batch([D[0], D[2]], [D[1], D[3]], [X, Y], [0, 0]), 0, [None] * 4),
+        ("copy_local_batch of no bytes, unaligned", xmpi.PROF_COPY, lambda: comm.copy_local_batch([D[0], D[2]], None, [Yodd, Y], [0, 0]), 0, [None] * 4),
+    ]
+    comm.set_param("kernel_mode", -1)  # (the events are the launchers' host side: the same for every variant)
+    comm.set_param("grid_cap", 0)
+    comm.prof_reset()
+    for what, counter, call, nbytes, expect in calls:
+        n0, ms0, b0 = comm.prof_get(counter)
+        dst.reset()
+        call()
+        n1, ms1, b1 = comm.prof_get(counter)
+        where = f"profiling on, {what}"
+        assert n1 == n0 + 1, f"{where}: prof_get counts {n1 - n0} launches"
+        assert b1 - b0 == nbytes, f"{where}: {b1 - b0} bytes accounted, expected {nbytes}"
+        assert ms1 >= ms0, f"{where}: the time went backwards"
+        if nbytes == 0:
+            assert ms1 - ms0 < 1.0, f"{where}: {ms1 - ms0:.3f} ms for a call that launched nothing"
+        outs = dst.get(where)
+        for k, e in enumerate(expect):
+            assert outs[k] == (b"\xEE" * (17 * es) if e is None else e), f"{where}: destination {k}"
+        run.launches += 1
+    assert src.get("profiling") == [t.tobytes() for t in (x, y, z, y)], "profiling: a source was modified"
+    comm.prof_enable(False)
+    src.free()
+    dst.free()
+
+
+KV_PARTS = {
+    "reduce2": [kv_reduce2],
+    "reduce_n": [lambda run: kv_reduce_n(run, (2, 3, 8))],
+    "reduce_n_generic": [lambda run: kv_reduce_n(run, (9, 16))],
+    "multi": [lambda run: kv_multi(run, ((1, 1), (3, 1), (8, 8)))],
+    "multi_wide": [lambda run: kv_multi(run, ((5, 7), (12, 3)))],
+    "copy": [kv_copy],
+    "batch": [kv_batch_reduce, kv_batch_copy],
+    "verify": [kv_verify, kv_profile],
+}
+
+
+def sc_kernel_variants(comm, args):
+    """One rank.  The local kernels under every (kernel_mode, grid_cap) of {0, 1, 2} x {0, 1, 3} -- each (T, OP, MODE) is machine
+    code of its own, and only a capped grid takes a block through a second tile -- against the CPU oracle: dense float and integer
+    data bit for bit, special floats under same_floats, copies and checksums against numpy / the oracle; guard bytes round every
+    destination; sources that are not a destination unchanged; on dense and integer data all nine variants the same bytes (on
+    special data: reported).  args["part"]: one of KV_PARTS (the matrix is cut by kernel family, no case is left out), default all."""
+    assert comm.size() == 1, "kernel_variants is a one-rank scenario"
+    run = KvRun(comm)
+    parts = [args["part"]] if args.get("part") else list(KV_PARTS)
+    for part in parts:
+        for fn in KV_PARTS[part]:
+            fn(run)
+    comm.set_param("kernel_mode", -1)
+    comm.set_param("grid_cap", 0)
+    differ = {k: v for k, v in run.special.items() if v[0]}
+    print(f"kernel_variants {'+'.join(parts)}: {run.launches} launches over {len(KV_VARIANTS)} (kernel_mode, grid_cap) pairs held to the oracle, "
+          f"{run.cases} cases; on special data the nine variants' bytes "
+          + ("are identical in every case" if not differ else "DIFFER: " + ", ".join(f"{k}: {v[1]} elements in {v[0]} cases" for k, v in sorted(differ.items()))))
+
+
 SCENARIOS = {
     "guard": sc_guard,
     "corrupt": sc_corrupt,
@@ -3321,4 +3845,5 @@ SCENARIOS = {
     "stream_ordered": sc_stream_ordered,
     "lifecycle_stress": sc_lifecycle_stress,
     "hard_floats": sc_hard_floats,
+    "kernel_variants": sc_kernel_variants,
 }

@@ -208,6 +208,38 @@ def test_gpu_scenarios_on_virtual_devices(devsim_lib, scenario, size, args):
     run_ranks(scenario, size, args, timeout=600, env={"DEVSIM_DEVICES": "8"} if size > 8 else None)
 
 
+# The streaming kernels' cache-policy variants (kernel_mode 0 / 1 / 2: separate instantiations) and their grid-stride loops
+# (grid_cap), which no other test shape reaches: the local kernels and the batch launchers under all nine pairs, then the
+# collectives that run them -- the split form's body kernel, the zero-copy fold, reduce2_batch through the staged tables,
+# copy_batch as the transport -- non-temporal and with every block looping (the knobs are process-wide: child processes).
+_STAGED = {"XMPI_DSYNC": "0", "XMPI_ZERO_COPY": "0"}
+_BATCHED = {"XMPI_COPY_ENGINE": "1", "XMPI_BATCH_COPIES": "1", "XMPI_DSYNC": "0"}
+VARIANTS = [("kernel_variants", 1, {"part": part}, None) for part in ("reduce2", "reduce_n", "reduce_n_generic", "multi", "multi_wide", "copy", "batch", "verify")]
+for _mode in (1, 2):
+    _p = {"kernel_mode": _mode, "grid_cap": 3}
+    VARIANTS += [
+        ("split", 2, {"counts": [1, 17, 4099, 65536 + 5], "params": _p}, None),
+        ("hard_floats", 3, {"params": _p}, None),
+        ("hard_floats", 3, {"expect_staged": 1, "expect_params": {"dsync": 0, "zero_copy": 0}, "params": _p}, _STAGED),
+        ("allreduce_small", 2, {"counts": [1, 4099, 65536 + 5], "params": _p}, _BATCHED),
+        ("allgather", 2, {"counts": [1, 4099, 65536 + 5], "params": _p}, _BATCHED),
+    ]
+
+
+def _variant_id(v):
+    scenario, size, args, env = v
+    return "-".join([scenario, str(size)] + ([args["part"]] if "part" in args else [f"mode{args['params']['kernel_mode']}"]) +
+                    (["staged"] if env is _STAGED else ["batched"] if env is _BATCHED else []))
+
+
+@pytest.mark.parametrize("scenario,size,args,env", VARIANTS, ids=[_variant_id(v) for v in VARIANTS])
+def test_kernel_variants_on_virtual_devices(devsim_lib, scenario, size, args, env):
+    if scenario == "kernel_variants":
+        from tests import scenarios
+        assert args["part"] in scenarios.KV_PARTS and len(scenarios.KV_PARTS) == 8
+    run_ranks(scenario, size, args, timeout=600, env=env)
+
+
 @pytest.mark.parametrize("devices,ranks", [(1, 4), (4, 4), (3, 3), (8, 8)])
 def test_no_kernel_touches_a_byte_past_its_buffers(devsim_lib, devices, ranks):
     """every buffer ends on the last byte of a page with an inaccessible page behind it (runtime.cpp devsim_guarded_alloc): the local
@@ -220,6 +252,10 @@ def test_no_kernel_touches_a_byte_past_its_buffers(devsim_lib, devices, ranks):
     cmd = [sys.executable, os.path.join(ROOT, "tests", "rank_worker.py"), "--threads", "guard", str(ranks)]
     p = subprocess.run(cmd + ['{"counts": [1, 17, 4099]}' if ranks == 8 else "{}"], cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert p.returncode == 0 and f"{ranks} rank threads guard: ok" in p.stdout, p.stdout[-4000:]
+    if devices == 1:  # ... non-temporal and under a grid cap: a looping block that rounds a tile up hits the guard page
+        p = subprocess.run(cmd + ['{"counts": [1, 17, 4099], "params": {"kernel_mode": 1, "grid_cap": 3}}'], cwd=ROOT, env=e, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=900)
+        assert p.returncode == 0 and f"{ranks} rank threads guard: ok" in p.stdout, p.stdout[-4000:]
     if devices == 1:  # ... and the guard is real: a checksum asked for one byte more than the buffer has dies of it
         p = subprocess.Popen(cmd[:-1] + ["1", '{"overrun": 1}'], cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         out, _ = p.communicate(timeout=300)

@@ -349,3 +349,49 @@ def test_rank_threads_in_different_calls_get_an_error_not_a_hang(what):
     """... and where ranks meet on the host (threads of one process): the descriptors they publish carry the same signature"""
     out = run_threads("mismatch", 3, {"what": what, "threads": 1}, timeout=120)
     assert out.count("ok (error after") == 3, out
+
+
+# ---- the cache-policy variants and the capped grids of the streaming kernels -----------------------------------------------------------
+# (the knobs are process-wide: every run below is a child process of its own)
+KERNEL_VARIANT_PARTS = ["reduce2", "reduce_n", "reduce_n_generic", "multi", "multi_wide", "copy", "batch", "verify"]
+
+
+@pytest.mark.parametrize("part", KERNEL_VARIANT_PARTS)
+def test_local_kernels_under_every_cache_policy_and_grid_cap(part):
+    """every local kernel and both batch launchers under kernel_mode 0 / 1 / 2 x grid_cap 0 / 1 / 3 at the sizes where a loop or a
+    branch changes, every dtype and operator, in place, unaligned, against the CPU oracle; the verification kernels under the caps; the
+    profiled entries at no elements (tests/scenarios.py sc_kernel_variants, one kernel family per case)"""
+    from tests import scenarios
+    assert sorted(scenarios.KV_PARTS) == sorted(KERNEL_VARIANT_PARTS)
+    out = run_ranks("kernel_variants", 1, {"part": part}, timeout=300)[0]
+    print("\n".join(ln for ln in out.splitlines() if ln.startswith("kernel_variants")))  # (what the variants' bytes did on special data)
+
+
+def variant(mode, **args):
+    return dict(args, params={"kernel_mode": mode, "grid_cap": 3})
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_split_form_under_the_variants(mode):
+    """the body kernel's non-temporal instantiations (sched.hip dsync_body_kernel: kernel_mode 1 and 2)"""
+    run_ranks("split", 2, variant(mode, counts=[1, 17, 4099, 65536 + 5]), timeout=300)
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_hard_floats_under_the_variants(mode):
+    run_ranks("hard_floats", 3, variant(mode), timeout=300)
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_hard_floats_through_the_staged_tables_under_the_variants(mode):
+    """XMPI_DSYNC=0 XMPI_ZERO_COPY=0: reduce2_batch as the step tables call it, non-temporal, every block looping"""
+    run_ranks("hard_floats", 3, variant(mode, expect_staged=1, expect_params={"dsync": 0, "zero_copy": 0}), timeout=300,
+              env={"XMPI_DSYNC": "0", "XMPI_ZERO_COPY": "0"})
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_batched_copies_under_the_variants(mode):
+    """the copy kernel as transport, all ready pushes and slot drains of a rank in one copy_batch launch"""
+    env = {"XMPI_COPY_ENGINE": "1", "XMPI_BATCH_COPIES": "1", "XMPI_DSYNC": "0"}
+    run_ranks("allreduce_small", 2, variant(mode, counts=[1, 4099, 65536 + 5]), timeout=300, env=env)
+    run_ranks("allgather", 2, variant(mode, counts=[1, 4099, 65536 + 5]), timeout=300, env=env)

@@ -81,6 +81,20 @@ func Alltoall(send, recv interface{}) error {
 	return errNoCollectives
 }
 
+// PersonalV is implemented by backends that also provide the all-to-all with a count per pair.
+type PersonalV interface {
+	Alltoallv(send interface{}, sendcounts, sdispls []uint64, recv interface{}, recvcaps, rdispls []uint64) ([]uint64, error)
+}
+
+// Alltoallv is the exchange examples/helloworld/helloworld.go:53-81 really performs -- messages of different lengths, the receiver
+// learning the length as Receive does (network.go:594-601) -- as one call; it returns the counts received.
+func Alltoallv(send interface{}, sendcounts, sdispls []uint64, recv interface{}, recvcaps, rdispls []uint64) ([]uint64, error) {
+	if c, ok := mpier.(PersonalV); ok {
+		return c.Alltoallv(send, sendcounts, sdispls, recv, recvcaps, rdispls)
+	}
+	return nil, errNoCollectives
+}
+
 // Barrier blocks until every rank has called it.
 func Barrier() error {
 	if c, ok := mpier.(Collective); ok {

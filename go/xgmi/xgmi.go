@@ -380,6 +380,24 @@ func (b *Backend) Alltoall(send, recv interface{}) error {
 	return status(C.xmpi_alltoall(b.comm, sp, rp, C.size_t(n/size), C.xmpi_dtype(dt), 0), "mpi alltoall")
 }
 
+// Alltoallv is the exchange helloworld.go:53-81 really performs: a count per pair (elements of send's type), the receiver learning
+// it as Receive does (network.go:594-601).  sendcounts[j] elements from send[sdispls[j]:] go to rank j; what rank r sends lands at
+// recv[rdispls[r]:] if it is at most recvcaps[r] elements.  Returns what every rank sent.  Out of place.
+func (b *Backend) Alltoallv(send interface{}, sendcounts, sdispls []uint64, recv interface{}, recvcaps, rdispls []uint64) ([]uint64, error) {
+	sp, sn, dt, ok1 := view(send)
+	rp, rn, _, ok2 := view(recv)
+	if !ok1 || !ok2 {
+		return nil, errPayload
+	}
+	size := b.Size()
+	if size < 1 || len(sendcounts) != size || len(sdispls) != size || len(recvcaps) != size || len(rdispls) != size {
+		return nil, errBlocks
+	}
+	got := make([]uint64, size)
+	err := status(C.xmpi_alltoallv(b.comm, sp, C.size_t(sn), (*C.uint64_t)(unsafe.Pointer(&sendcounts[0])), (*C.uint64_t)(unsafe.Pointer(&sdispls[0])), rp, C.size_t(rn), (*C.uint64_t)(unsafe.Pointer(&recvcaps[0])), (*C.uint64_t)(unsafe.Pointer(&rdispls[0])), (*C.uint64_t)(unsafe.Pointer(&got[0])), C.xmpi_dtype(dt), 0), "mpi alltoallv")
+	return got, err
+}
+
 // Barrier is a host-side rendezvous of all ranks.
 func (b *Backend) Barrier() error { return status(C.xmpi_barrier(b.comm), "mpi barrier") }
 
@@ -451,6 +469,10 @@ func (b *Backend) ReduceScatterOnStream(send, recv DeviceBuffer, op int, stream 
 func (b *Backend) AlltoallOnStream(send, recv DeviceBuffer, blockCount int, stream unsafe.Pointer) error {
 	return status(C.xmpi_alltoall_on_stream(b.comm, send.Ptr, recv.Ptr, C.size_t(blockCount), C.xmpi_dtype(send.Type),
 		stream), "mpi alltoall")
+}
+// AlltoallvOnStream: the five arrays are DEVICE buffers of Size() uint64 each, read and written when the kernel runs.
+func (b *Backend) AlltoallvOnStream(send DeviceBuffer, sendcounts, sdispls DeviceBuffer, recv DeviceBuffer, recvcaps, rdispls, recvcounts DeviceBuffer, stream unsafe.Pointer) error {
+	return status(C.xmpi_alltoallv_on_stream(b.comm, send.Ptr, C.size_t(send.Count), (*C.uint64_t)(sendcounts.Ptr), (*C.uint64_t)(sdispls.Ptr), recv.Ptr, C.size_t(recv.Count), (*C.uint64_t)(recvcaps.Ptr), (*C.uint64_t)(rdispls.Ptr), (*C.uint64_t)(recvcounts.Ptr), C.xmpi_dtype(send.Type), stream), "mpi alltoallv")
 }
 func (b *Backend) BcastOnStream(buf DeviceBuffer, root int, stream unsafe.Pointer) error {
 	return status(C.xmpi_bcast_on_stream(b.comm, buf.Ptr, C.size_t(buf.Count), C.xmpi_dtype(buf.Type), C.int(root), stream), "mpi bcast")

@@ -189,7 +189,8 @@ int xmpi_sync(xmpi_comm* comm);
  * slice, and into a device destination by DMA out of the lane.  That copy is one kernel whose last block writes both acknowledgements itself, and which stays for
  * p2p_agent_us (XMPI_P2P_AGENT_US, default 40; 0 = one launch per message) after a message to take the next one from a command
  * record in pinned host memory instead of being launched again: between two processes a small message takes 4.5-5 us per
- * direction.  Nothing on the GPU ever waits for a peer on this path. */
+ * direction.  Nothing on the GPU ever waits for a peer on this path.  One tag, INT32_MIN, is the library's own
+ * (xmpi_alltoallv with ranks that meet on the host moves its blocks under it): xmpi_send / _send_nowait / _recv refuse it, XMPI_ERR_ARG. */
 int xmpi_send(xmpi_comm* comm, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag);
 
 /* The split of Send the reference's author sketched and left commented out (mpi.go:132-152):
@@ -354,6 +355,43 @@ int xmpi_reduce_scatter_on_stream(xmpi_comm* comm, const void* sendbuf, void* re
                                   xmpi_dtype dtype, xmpi_op op, void* stream);
 int xmpi_alltoall_on_stream(xmpi_comm* comm, const void* sendbuf, void* recvbuf, size_t count,
                             xmpi_dtype dtype, void* stream);
+
+/* (absent from the reference's API, mpi.go:130 -- but this, not the equal-count call above, is the exchange its own program performs,
+ * helloworld.go:53-81: the message a rank sends itself has another length than the one it sends a peer, and Receive re-sizes the
+ * destination to whatever arrived, network.go:594-601)  An all-to-all with a count per pair, the receiver learning it from the
+ * exchange.  All counts, displacements and extents in ELEMENTS of dtype; the five arrays have `size` entries.  Rank `me` sends
+ * sendcounts[j] elements from sendbuf + sdispls[j] to rank j; what rank r sends lands at recvbuf + rdispls[r], provided it is at
+ * most recvcaps[r] elements; recvcounts[r] (out) is the count r sent -- also when it was too long to be accepted.  Zero counts are
+ * legal everywhere.  send_extent / recv_extent are the sizes of the two buffers: no byte outside them is read or written, whatever
+ * the arrays say, and bytes of recvbuf outside the delivered blocks keep their values.  Out of place only (the extents overlap:
+ * XMPI_ERR_ARG).  An allgather-v is all sdispls equal, all sendcounts equal.
+ * A pair whose count exceeds the receiver's capacity moves nothing in that direction and gives XMPI_ERR_TRUNCATE on both its ranks;
+ * a row of the arrays that leaves the extents is announced to that peer as nothing sent, nothing accepted, and gives XMPI_ERR_ARG
+ * on this rank.  Every other pair proceeds, xmpi_last_error names the peer, and the communicator stays usable (as after a truncated
+ * xmpi_recv).
+ * Blocking form: the five arrays are host memory.  algo: ZCOPY | DIRECT | AUTO (anything else: XMPI_ERR_UNSUPPORTED).  One process
+ * per GPU: ONE kernel per rank exchanges the counts between the ranks' kernels and stores every block straight into its receiver's
+ * buffer; host slices and unregistered memory are stood in for.  Ranks that meet on the host (and DIRECT): the pairs through
+ * xmpi_alltoall, the blocks over Send / Receive -- under a tag xmpi_send / xmpi_recv refuse (INT32_MIN). */
+int xmpi_alltoallv(xmpi_comm* comm, const void* sendbuf, size_t send_extent,
+                   const uint64_t* sendcounts, const uint64_t* sdispls,
+                   void* recvbuf, size_t recv_extent,
+                   const uint64_t* recvcaps, const uint64_t* rdispls,
+                   uint64_t* recvcounts, xmpi_dtype dtype, int algo);
+
+/* (no counterpart in the reference; the exchange is helloworld.go:53-81's, the re-sizing Receive network.go:594-601)  The
+ * stream-ordered form: the five arrays must be addressable by the DEVICE (device memory or pinned host memory) and are read and
+ * written when the kernel runs, in stream order -- not when the call is made: counts a kernel produced never come to the host, and
+ * a captured graph (xmpi_graph_begin: registered buffers, everything mapped by one call before the capture) reads them afresh at
+ * every replay.  Needs ranks that meet on the device; XMPI_ERR_UNSUPPORTED otherwise, as xmpi_send_on_stream; arrays the device
+ * cannot address (pageable host memory): XMPI_ERR_ARG.  A truncated pair or a row out of its extents is reported by the
+ * xmpi_stream_sync behind it -- or, like every failure of an enqueued collective, by whichever BLOCKING collective of this
+ * communicator completes first: sync the stream before the next blocking call to have the report where it belongs. */
+int xmpi_alltoallv_on_stream(xmpi_comm* comm, const void* sendbuf, size_t send_extent,
+                             const uint64_t* sendcounts, const uint64_t* sdispls,
+                             void* recvbuf, size_t recv_extent,
+                             const uint64_t* recvcaps, const uint64_t* rdispls,
+                             uint64_t* recvcounts, xmpi_dtype dtype, void* stream);
 
 /* ---- local kernels (the HBM-bound pieces, exposed for parity tests and rooflines) --------- */
 

@@ -44,6 +44,10 @@ int xmpi_sched_dump(int sched, int form, int in_place, int size, int rank, int r
 /* Bytes of the landing block `rank` lends to the push form of that schedule (0: none). */
 size_t xmpi_sched_land_bytes(int sched, int in_place, int size, int rank, int root, size_t count, size_t elem_size);
 
+/* xmpi_alltoallv with ranks that meet on the host moves its blocks in `size` rounds of disjoint pairs: the partner of `rank` in
+ * round `round` (a rank may be its own).  Host logic only; -1 for arguments out of range. */
+int xmpi_alltoallv_partner(int round, int rank, int size);
+
 /* Chunk j of a count-element buffer cut for `size` ranks the way the zero-copy collectives cut it
  * (16-byte aligned boundaries): element offset and length.  Host logic only. */
 int xmpi_zc_chunk(size_t count, size_t elem_size, int size, int j, size_t* elem_off, size_t* elem_cnt);

@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra"]
 
-LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "p2p.cpp", "agent.cpp", "api.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "dsync_conn.cpp", "trace.cpp"]
+LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "p2p.cpp", "agent.cpp", "api.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "dsync_conn.cpp", "vcoll.cpp", "trace.cpp"]
 LIB_HEADERS = ["kernels.h", "kdev.h", "sched_steps.h", "comm.h", "ctl.h", "plan.h", "trace.h", os.path.join("..", "..", "include", "xmpi.h"),
                os.path.join("..", "..", "include", "xmpi_test.h")]
 
@@ -133,7 +133,8 @@ def build_host(force: bool = False) -> list[str]:
                           ("allreduce_bench", os.path.join(ROOT, "examples", "allreduce_bench.cpp")),
                           ("cfg5_sweep", os.path.join(ROOT, "examples", "cfg5_sweep.cpp")),
                           ("cfg3_allgather", os.path.join(ROOT, "examples", "cfg3_allgather.cpp")),
-                          ("alltoall", os.path.join(ROOT, "examples", "alltoall.cpp"))):
+                          ("alltoall", os.path.join(ROOT, "examples", "alltoall.cpp")),
+                          ("alltoallv", os.path.join(ROOT, "examples", "alltoallv.cpp"))):
             if os.path.exists(src):
                 out = os.path.join(BIN, name)
                 if force or _newer(out, [src] + deps):

@@ -418,8 +418,8 @@ int xmpi_sync(xmpi_comm* c) {
 int xmpi_send(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) {
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
-  if (!es || dest < 0 || dest >= c->size || (count && !buf)) {
-    set_last_error("send: bad dtype / destination / buffer");
+  if (!es || dest < 0 || dest >= c->size || (count && !buf) || tag == kVTag) {
+    set_last_error("send: bad dtype / destination / buffer (or the one tag the library keeps to itself)");
     return XMPI_ERR_ARG;
   }
   return why_peer(c, p2p_send(c, buf, count * es, (int)dtype, dest, tag), "send");
@@ -428,8 +428,8 @@ int xmpi_send(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int
 int xmpi_send_nowait(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) {
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
-  if (!es || dest < 0 || dest >= c->size || (count && !buf)) {
-    set_last_error("send: bad dtype / destination / buffer");
+  if (!es || dest < 0 || dest >= c->size || (count && !buf) || tag == kVTag) {
+    set_last_error("send: bad dtype / destination / buffer (or the one tag the library keeps to itself)");
     return XMPI_ERR_ARG;
   }
   return why_peer(c, p2p_send(c, buf, count * es, (int)dtype, dest, tag, /*wait_ack=*/false), "send");
@@ -444,8 +444,8 @@ int xmpi_wait(xmpi_comm* c, int dest, int tag) {
 int xmpi_recv(xmpi_comm* c, void* buf, size_t capacity, xmpi_dtype dtype, int src, int tag, size_t* got) {
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
-  if (!es || src < 0 || src >= c->size || (capacity && !buf)) {
-    set_last_error("receive: bad dtype / source / buffer");
+  if (!es || src < 0 || src >= c->size || (capacity && !buf) || tag == kVTag) {
+    set_last_error("receive: bad dtype / source / buffer (or the one tag the library keeps to itself)");
     return XMPI_ERR_ARG;
   }
   size_t got_bytes = 0;
@@ -905,6 +905,7 @@ long xmpi_get_param(const xmpi_comm* c, const char* name) {
   if (n == "ll_bytes") return c->ll_bytes;
   if (n == "ll_max_bytes") return (long)kLLMaxPayload;
   if (n == "dsync_ll_launches") return (long)c->dsync_ll_launches;
+  if (n == "dsync_v_launches") return (long)c->dsync_v_launches;
   if (n == "agent_ll") return c->agent_ll;
   if (n == "agent_ll_bytes") return c->agent_ll_bytes;
   if (n == "ll_agent_us") return c->ll_agent_us;

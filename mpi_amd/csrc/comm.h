@@ -212,6 +212,9 @@ struct xmpi_comm {
   uint64_t dsync_launches = 0, dsync_bounced = 0;  // diagnostics: kernels; buffers stood in for by arena blocks
   long ll_bytes = 0;             // untuned AUTO: collectives up to this many bytes per rank go as LL lines (ll.hip); XMPI_LL_BYTES
   uint64_t dsync_ll_launches = 0;  // ... collectives that did
+  uint64_t dsync_v_launches = 0;   // xmpi_alltoallv calls whose counts the kernel read and exchanged (dsync_alltoallv)
+  uint64_t* v_rec = nullptr;       // pinned record of a blocking xmpi_alltoallv: its five arrays, kDsyncRanks words each ...
+  uint64_t* v_rec_dev = nullptr;   // ... as the device addresses it
   long agent_ll = 1;             // a BLOCKING LL collective of up to agent_ll_bytes per rank is handed to the lingering LL agent
   long agent_ll_bytes = 8192;    // (ll.hip ll_agent_kernel) instead of being launched; XMPI_AGENT_LL, XMPI_AGENT_LL_BYTES
   long ll_agent_us = 40;         // how long that kernel lingers after a collective; XMPI_LL_AGENT_US (default: XMPI_P2P_AGENT_US's value)
@@ -303,6 +306,8 @@ struct xmpi_comm {
 namespace xmpi {
 int ensure_streams(xmpi_comm* c);
 int run_plan(xmpi_comm* c, const Plan& plan, const void* sendbuf, void* recvbuf, int dtype, int op);
+// the tag xmpi_alltoallv's host form sends its blocks under: the public Send / Receive refuse it, so no caller's message carries it
+constexpr int kVTag = -2147483647 - 1;
 int p2p_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest, int tag, bool wait_ack = true);
 int p2p_wait(xmpi_comm* c, int dest, int tag);
 int p2p_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, int tag, size_t* got_bytes);
@@ -389,6 +394,14 @@ bool dsync_usable(const xmpi_comm* c);
 int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,
                      int op, hipStream_t stream, bool blocking, int algo = 0);
 bool dsync_takes(const xmpi_comm* c, int coll, int algo);
+// xmpi_alltoallv with ranks that meet on the device.  The five arrays are memory the device addresses (`stream` form), or -- blocking,
+// host arrays -- go through the communicator's pinned record.  Extents and the arrays' contents in elements.
+struct VArrays {
+  const uint64_t *sendcounts, *sdispls, *recvcaps, *rdispls;
+  uint64_t* recvcounts;
+};
+int dsync_alltoallv(xmpi_comm* c, const void* sendbuf, size_t send_extent, void* recvbuf, size_t recv_extent, const VArrays& v, int dtype,
+                    hipStream_t stream, bool blocking);
 void dsync_graph_launched(xmpi_comm* c, hipStream_t stream, bool before);
 int dsync_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest, int tag, hipStream_t stream);
 int dsync_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, int tag, hipStream_t stream);

@@ -1238,6 +1238,153 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   return blocking ? call.wait_and_finish(recvbuf, k.recv_bytes) : call.enqueued(recvbuf, k.recv_bytes);
 }
 
+// ---- xmpi_alltoallv: every pair its own count, read and exchanged by the kernel ---------------------------------------------------
+// What the reference's own program does (helloworld.go:53-81: messages of different lengths, and Receive re-sizes the destination to
+// whatever arrived, network.go:594-601) as ONE kernel per rank (kernels.hip dsync_alltoallv_kernel).  The host knows the two EXTENTS
+// only: it announces them like any collective's buffers and sizes the grid from the send extent; counts and displacements are read
+// by the kernel when it runs -- from the caller's device arrays (stream form: a captured launch replays with whatever they hold
+// then), or from the communicator's pinned record a blocking call fills.
+// Only meet-on-the-device, one kernel: the split (meet / body / done) form and an LL-line form do not exist for it.
+namespace {
+enum { VREC_SENDCOUNTS = 0, VREC_SDISPLS = 1, VREC_RECVCAPS = 2, VREC_RDISPLS = 3, VREC_RECVCOUNTS = 4, VREC_ARRAYS = 5 };
+
+// a buffer of the call the peers can map: the caller's, or -- host memory, unregistered device memory, nothing at all (an extent
+// of 0) -- a registered stand-in of the extent's size, lent into `lent`
+void* v_mappable(xmpi_comm* c, std::vector<void*>& lent, const void* p, size_t bytes, BufRef* ref, bool* stood_in, int* rc) {
+  *stood_in = false;
+  if (bytes > 0 && zc_export(c, p, bytes, ref)) return const_cast<void*>(p);
+  *stood_in = true;
+  return lend_standin(c, lent, std::max<size_t>(bytes, 16), ref, rc);
+}
+}  // namespace
+
+int dsync_alltoallv(xmpi_comm* c, const void* sendbuf, size_t send_extent, void* recvbuf, size_t recv_extent, const VArrays& v, int dtype,
+                    hipStream_t stream, bool blocking) {
+  const int N = c->size;
+  const size_t es = xmpi_dtype_size((xmpi_dtype)dtype), sb = send_extent * es, rb = recv_extent * es;
+  if (!stream) stream = c->local_stream;
+  DsyncCall call(c, stream, blocking);
+  dsync_service(c);
+  reap_deferred(c, false);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(stream, &cap);
+  (void)hipGetLastError();
+  const bool capturing = cap != hipStreamCaptureStatusNone;
+  RoctxRange range("xmpi:dsync alltoallv send_extent=%zu recv_extent=%zu epoch=%llu %s", sb, rb, (unsigned long long)c->dsync_epoch + 1,
+                   blocking ? "blocking" : capturing ? "captured" : "enqueued");
+
+  // the arrays the kernel reads: the caller's (stream form), or the pinned record
+  VArrays dv = v;
+  if (blocking) {
+    if (!c->v_rec) pinned_words(sizeof(uint64_t) * VREC_ARRAYS * kDsyncRanks, &c->v_rec, &c->v_rec_dev);
+    if (!c->v_rec || !c->v_rec_dev) {
+      set_last_error("alltoallv: no pinned memory for the record of counts");
+      return XMPI_ERR_NOMEM;
+    }
+    const uint64_t* in[4] = {v.sendcounts, v.sdispls, v.recvcaps, v.rdispls};
+    for (int k = 0; k < 4; k++) memcpy(c->v_rec + k * kDsyncRanks, in[k], sizeof(uint64_t) * (size_t)N);
+    memset(c->v_rec + VREC_RECVCOUNTS * kDsyncRanks, 0, sizeof(uint64_t) * kDsyncRanks);
+    dv.sendcounts = c->v_rec_dev + VREC_SENDCOUNTS * kDsyncRanks;
+    dv.sdispls = c->v_rec_dev + VREC_SDISPLS * kDsyncRanks;
+    dv.recvcaps = c->v_rec_dev + VREC_RECVCAPS * kDsyncRanks;
+    dv.rdispls = c->v_rec_dev + VREC_RDISPLS * kDsyncRanks;
+    dv.recvcounts = c->v_rec_dev + VREC_RECVCOUNTS * kDsyncRanks;
+  }
+
+  // the buffers: stand-ins of the extents' size for what the peers cannot map.  A blocking call keeps its receive stand-in past
+  // the wait (`keep`) and copies down the delivered blocks alone; an enqueued one, which has no counts, loads the stand-in from the
+  // receive buffer first and copies it back whole (DsyncCall::enqueued), so what lies between the blocks survives.
+  std::vector<void*> keep;
+  auto give_back = [&keep](int rc) {
+    for (void* p : keep) (void)heap_free(p);
+    keep.clear();
+    return rc;
+  };
+  Resolved r;
+  int rc = XMPI_OK;
+  bool s_in = false, r_in = false;
+  // (probe without lending: a capture must fail before anything is borrowed)
+  if (capturing) {
+    BufRef probe;
+    if (!sb || !rb) {
+      set_last_error("graph capture: an extent of 0 is stood in for by a block lent for the call, which a graph cannot hold (pass a registered "
+                     "buffer of at least one element)");
+      return XMPI_ERR_ARG;
+    }
+    if (!zc_export(c, sendbuf, sb, &probe) || !zc_export(c, recvbuf, rb, &probe)) {
+      set_last_error("graph capture needs registered device buffers (xmpi_malloc / xmpi_register)");
+      return XMPI_ERR_ARG;
+    }
+  }
+  r.send = v_mappable(c, call.lent, sendbuf, sb, &r.sref, &s_in, &rc);
+  if (!r.send) return call.fail(rc);
+  if (s_in && sb) {
+    const hipError_t e = hipMemcpyAsync(const_cast<void*>(r.send), sendbuf, sb, hipMemcpyDefault, stream);
+    if (e != hipSuccess) return call.fail(hip_fail(e, "copy into a stand-in", __FILE__, __LINE__));
+  }
+  r.recv = v_mappable(c, blocking ? keep : call.lent, recvbuf, rb, &r.rref, &r_in, &rc);
+  if (!r.recv) return give_back(call.fail(rc));
+  if (r_in && rb && !blocking) {
+    const hipError_t e = hipMemcpyAsync(r.recv, recvbuf, rb, hipMemcpyDefault, stream);
+    if (e != hipSuccess) return call.fail(hip_fail(e, "copy into a stand-in", __FILE__, __LINE__));
+    call.out_src = r.recv;
+  }
+  int sslot = 0, rslot = 0;
+  rc = announce(c, r, capturing, &sslot, &rslot);
+  if (rc == XMPI_OK) rc = order_behind_last(c, stream, capturing);
+  if (rc != XMPI_OK) return give_back(call.fail(rc));
+
+  call.begin(capturing);
+  DsyncVArgs va;
+  memset(&va, 0, sizeof va);
+  va.d = meet_args(c, r, sslot, rslot);
+  // (the collective and the element size: the counts are nobody's to compare before the kernels have exchanged them)
+  va.d.sig = sig_fold(sig_mix(sig_mix(0x9E3779B97F4A7C15ull, (uint64_t)COLL_COUNT + 1), (uint64_t)es));
+  va.d.host_done = call.done_dev;
+  va.d.done_value = call.done_id;
+  va.sendcounts = dv.sendcounts;
+  va.sdispls = dv.sdispls;
+  va.recvcaps = dv.recvcaps;
+  va.rdispls = dv.rdispls;
+  va.recvcounts = dv.recvcounts;
+  va.send_extent = send_extent;
+  va.recv_extent = recv_extent;
+  va.vstatus = c->dsync_status_dev ? c->dsync_status_dev + 13 : nullptr;
+  if (!call.prof_events()) return give_back(call.fail(XMPI_ERR_HIP));
+  ++c->dsync_epoch;
+  {
+    // the host may not know the counts: the grid follows the send extent (every block strides over whatever tiles there are)
+    const int gx = dsync_grid(c, sb / 16, 1, 4);
+    const hipError_t le = launch_dsync_alltoallv(va, (int)es, gx, stream, call.pstart, call.pstop);
+    if (le != hipSuccess) {
+      --c->dsync_epoch;
+      return give_back(call.fail(hip_fail(le, "alltoallv kernel launch", __FILE__, __LINE__)));
+    }
+  }
+  c->dsync_launches++;
+  c->dsync_v_launches++;
+  if (!capturing) c->dsync_last_stream = stream;
+  call.traffic = 2 * sb;
+  if (!blocking) return call.enqueued(recvbuf, rb);
+
+  rc = call.wait_and_finish(nullptr, 0);
+  if (rc != XMPI_OK && rc != XMPI_ERR_TRUNCATE && rc != XMPI_ERR_ARG) return give_back(rc);
+  const uint64_t* got = c->v_rec + VREC_RECVCOUNTS * kDsyncRanks;
+  memcpy(v.recvcounts, got, sizeof(uint64_t) * (size_t)N);
+  if (r_in) {  // the delivered blocks go home: rows that held, counts that fitted
+    hipError_t e = hipSuccess;
+    for (int p = 0; p < N && e == hipSuccess; p++) {
+      const bool row_ok = v.sdispls[p] <= send_extent && v.sendcounts[p] <= send_extent - v.sdispls[p] && v.rdispls[p] <= recv_extent &&
+                          v.recvcaps[p] <= recv_extent - v.rdispls[p];
+      if (!row_ok || got[p] == 0 || got[p] > v.recvcaps[p]) continue;
+      e = hipMemcpyAsync((char*)recvbuf + v.rdispls[p] * es, (const char*)r.recv + v.rdispls[p] * es, got[p] * es, hipMemcpyDefault, stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return give_back(hip_fail(e, "copy of a stand-in's delivered blocks", __FILE__, __LINE__));
+  }
+  return give_back(rc);
+}
+
 // ---- stream-ordered Send / Receive ------------------------------------------------------------------------------------
 // The reference's Send is a gob message on a net.Conn and a wait for the ack message (network.go:562-571), its Receive
 // reads, routes by tag, acks and decodes (network.go:575-625).  Here both are ONE kernel each, enqueued on a stream:
@@ -1410,6 +1557,18 @@ void dsync_prof_harvest(xmpi_comm* c) {
 int dsync_check(xmpi_comm* c) {
   if (!c->dsync_status) return XMPI_OK;
   const uint32_t st = __atomic_exchange_n(c->dsync_status, 0u, __ATOMIC_ACQ_REL);
+  // xmpi_alltoallv's own verdicts (DsyncVStatus, word 13): one pair's business -- the job is NOT aborted, the communicator stays
+  // usable, as after a truncated xmpi_recv; a timeout or an abort in the same kernel is what gets reported
+  const uint32_t vst = __atomic_exchange_n(c->dsync_status + 13, 0u, __ATOMIC_ACQ_REL);
+  if (st == DSYNC_OK && vst != 0) {
+    const std::string peer = std::to_string((int)(vst >> 8) - 1);
+    if ((vst & 0xffu) == DSYNC_BOUNDS) {
+      set_last_error("alltoallv: the arrays' row for rank " + peer + " leaves the extents of the buffers; nothing was moved between the two");
+      return XMPI_ERR_ARG;
+    }
+    set_last_error("alltoallv: the block exchanged with rank " + peer + " is longer than the capacity its receiver granted; it was not moved");
+    return XMPI_ERR_TRUNCATE;
+  }
   if (st == DSYNC_OK) return XMPI_OK;
   int rc = XMPI_ERR_PEER;
   if (st == DSYNC_TIMEOUT) {

@@ -330,6 +330,8 @@ void dsync_finalize(xmpi_comm* c) {
   c->host_bounce = c->host_bounce_dev = nullptr;
   if (c->dsync_status) (void)hipHostFree(c->dsync_status);
   c->dsync_status = nullptr;
+  if (c->v_rec) (void)hipHostFree(c->v_rec);
+  c->v_rec = c->v_rec_dev = nullptr;
   if (c->dsync_res) (void)hipFree(c->dsync_res);
   c->dsync_res = nullptr;
   if (c->dsync_order_ev) (void)hipEventDestroy(c->dsync_order_ev);

@@ -404,5 +404,9 @@ __device__ __forceinline__ uint64_t* step_flags(DsyncPage* page) {
   return reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(page) + kStepOff);
 }
 
+__device__ __forceinline__ VBox* vbox_of(DsyncPage* page) {
+  return reinterpret_cast<VBox*>(reinterpret_cast<char*>(page) + kVBoxOff);
+}
+
 }  // namespace
 }  // namespace xmpi

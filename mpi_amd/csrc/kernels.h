@@ -153,8 +153,20 @@ struct P2PGo {
   uint64_t pad[1];
 };
 constexpr size_t kGoOff = kTakenOff + sizeof(uint64_t) * kDsyncRanks * kP2PBoxes;
+//   [kVBoxOff, +512 B)     VBox vbox[kDsyncRanks]: vbox[p] is written by rank p only -- what p tells this rank about their pair in the
+//                           running xmpi_alltoallv (dsync_alltoallv_kernel)
+constexpr size_t kVBoxOff = kGoOff + sizeof(P2PGo) * kP2PGoSlots;
+struct VBox {
+  uint64_t epoch;   // written last (system-scope release, as DsyncSlot::epoch): the fields below belong to this collective
+  uint64_t count;   // elements the writer sends the owner (0: nothing, or the writer's row left its extents)
+  uint64_t rdispl;  // element displacement in the WRITER's receive buffer where the owner's block goes
+  uint64_t cap;     // elements the writer accepts from the owner
+  uint64_t valid;   // 0: the writer's row for the owner left its extents -- nothing moves between the two, in either direction
+  uint64_t pad[3];
+};
+static_assert(sizeof(VBox) == 64, "one box = one 64-byte record");
 constexpr size_t kLLHereOff = 768u << 10;
-static_assert(kGoOff + sizeof(P2PGo) * kP2PGoSlots <= kLLHereOff, "flag allocation");
+static_assert(kVBoxOff + sizeof(VBox) * kDsyncRanks <= kLLHereOff, "flag allocation");
 
 // ---- LL ("low latency") small collectives (ll.hip) -----------------------------------------------------------------------
 // The data IS the flag.  A rank pushes its payload straight into a slot of every peer's flag allocation as 16-byte lines
@@ -177,6 +189,10 @@ constexpr size_t kLLOff = 1u << 20;
 constexpr size_t kLLSlotBytes = 64u << 10;          // lines of one (source rank, parity)
 constexpr size_t kLLMaxPayload = kLLSlotBytes / 2;  // 32 KiB per rank
 static_assert(kLLHereOff + 64 * kDsyncRanks <= kLLOff, "flag allocation");
+// The v-boxes (VBox above) are single-buffered, and rank p may rewrite vbox[p] of rank q's allocation at its next xmpi_alltoallv:
+// a call completes on p only after q said "done" (kdev.h dsync_end), and every block of q read the box before it took the ticket
+// q's "done" waits for.  A box is matched by the collective's epoch, which only grows, and a communicator's epochs start above
+// what earlier users of the pooled pages left (DsyncArgs::epoch_floor): the pages need no clearing for the boxes either.
 static_assert(kLLOff + kLLSlotBytes * 2 * kDsyncRanks <= kDsyncPageBytes, "flag allocation");
 
 // what a block of the kernel moves: the fold of the source ranks' buffers (rank order) -> the destination ranks'
@@ -195,6 +211,10 @@ struct DsyncSeg {
 // once per L2 it relies on did not happen everywhere, the result cannot be trusted
 // DSYNC_MISMATCH: a peer announced another call than this rank's (DsyncArgs::sig: collective, schedule, bytes, dtype, operation, root).
 enum DsyncStatus : uint32_t { DSYNC_OK = 0, DSYNC_TIMEOUT = 1, DSYNC_ABORTED = 2, DSYNC_UNMAPPED = 3, DSYNC_XCD = 4, DSYNC_MISMATCH = 5 };
+// xmpi_alltoallv's own verdicts, kept apart from the above (DsyncVArgs::vstatus): they concern ONE pair, the rank's other blocks move
+// DSYNC_TRUNCATE: a block was longer than the capacity its receiver granted (both ends see it);  DSYNC_BOUNDS: a row of this rank's
+// arrays left the extents of its buffers.  The word: verdict | (peer + 1) << 8; BOUNDS wins over TRUNCATE, the lowest peer is named.
+enum DsyncVStatus : uint32_t { DSYNC_TRUNCATE = 1, DSYNC_BOUNDS = 2 };
 
 struct DsyncArgs {
   DsyncPage* page[kDsyncRanks];  // [me]: own page, others: the peers' pages as mapped here
@@ -268,6 +288,22 @@ hipError_t launch_ll_agent(const LLAgentArgs& a, hipStream_t stream);
 // all ranks sharing a GPU must be resident together); unroll = 16-byte packets per lane per source in flight
 hipError_t launch_dsync_fold(const DsyncArgs& a, int nsrc, int dtype, int op, int grid_x, int unroll, hipStream_t stream,
                              hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
+// xmpi_alltoallv (kernels.hip dsync_alltoallv_kernel): the counts are READ BY THE KERNEL, from memory the device addresses, when it
+// runs -- and exchanged between the ranks' kernels through the v-boxes.  All counts, displacements and extents in elements.
+struct DsyncVArgs {
+  DsyncArgs d;  // pages, this rank's announced buffers (the extents), epoch floor ... (nseg / seg unused)
+  const uint64_t* sendcounts;  // [n]: elements for rank j, at sdispls[j] of the send buffer
+  const uint64_t* sdispls;
+  const uint64_t* recvcaps;    // [n]: elements accepted from rank r, at rdispls[r] of the receive buffer
+  const uint64_t* rdispls;
+  uint64_t* recvcounts;        // [n] out: what rank r sent (offered, when it was too long to be accepted)
+  uint64_t send_extent, recv_extent;  // no byte outside the two buffers is read or written, whatever the arrays say
+  uint32_t* vstatus;           // host memory the GPU can write: DsyncVStatus word, may be null
+};
+// one gridDim.y == 1 launch of grid_x blocks (the caller bounds it as for launch_dsync_fold); elem_size 1 | 2 | 4 | 8
+hipError_t launch_dsync_alltoallv(const DsyncVArgs& a, int elem_size, int grid_x, hipStream_t stream, hipEvent_t ev_start = nullptr,
+                                  hipEvent_t ev_stop = nullptr);
 
 // one lane: *dst (pinned host memory, as the device addresses it) = *src (device memory), system-scope release -- in stream order
 hipError_t launch_word_to_host(uint64_t* dst, const uint64_t* src, hipStream_t stream);

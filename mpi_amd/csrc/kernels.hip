@@ -748,6 +748,148 @@ __global__ __launch_bounds__(kBlock) void dsync_fold_kernel(DsyncArgs a) {
   dsync_end(a, sh);
 }
 
+// ---- xmpi_alltoallv: the counts are exchanged INSIDE the kernel ---------------------------------------------------------------
+// dsync_begin as above (the buffers announced are the two EXTENTS), then lane t < n tells rank t about their pair through a v-box
+// in t's flag allocation (kernels.h VBox: what I send you, where your block goes in my receive buffer, how much I accept), waits
+// for t's box here and knows both directions: how much t sends (recvcounts[t]) and where its own block for t goes.  The copy runs
+// over ONE range of tiles -- the tiles of all n outgoing blocks numbered consecutively, destinations from `me` onwards as
+// plan_alltoall orders its segments -- which the grid's blocks stride over: a block finds a tile's segment from at most 8 prefix sums,
+// so a count matrix with one long block still uses the whole grid.  Loads and stores as the fold's copy segments (nt loads, nt
+// stores) on every path, the ragged ends and the one-element-per-lane path included.  A segment whose source and destination are congruent mod 16 moves as a head of under 16 bytes (none when both are
+// aligned), 16-byte packets and a tail; any other segment one element per lane.
+// A pair whose count exceeds the receiver's capacity moves nothing (both ends see it: DSYNC_TRUNCATE), a row of this rank's arrays
+// that leaves its extents is announced as nothing sent, nothing accepted (DSYNC_BOUNDS); the rank's other pairs proceed.
+template <int ES> struct VElem;
+template <> struct VElem<1> { typedef uint8_t type; };
+template <> struct VElem<2> { typedef uint16_t type; };
+template <> struct VElem<4> { typedef uint32_t type; };
+template <> struct VElem<8> { typedef uint64_t type; };
+struct VShared {
+  uint64_t src[kDsyncRanks], dst[kDsyncRanks], bytes[kDsyncRanks];  // segment d: my block for rank (me + d) % n
+  uint64_t tile0[kDsyncRanks + 1];                                  // the first tile of segment d; [n]: all of them
+  uint32_t trunc, bounds;                                           // kDsyncRanks - peer of the lowest peer concerned; 0: none
+};
+constexpr size_t kVTile = (size_t)kBlock * kUnroll;  // packets (elements, on the one-element-per-lane path) per tile
+
+template <int ES>
+__global__ __launch_bounds__(kBlock) void dsync_alltoallv_kernel(DsyncVArgs a) {
+  XMPI_SHARED(DsyncShared, sh);
+  XMPI_SHARED(VShared, vs);
+  const int t = threadIdx.x, me = a.d.me, n = a.d.n;
+  if (t == 0) vs.trunc = vs.bounds = 0;
+  dsync_begin(a.d, sh);
+  // (a block whose rendezvous failed still posts its boxes -- as "nothing, invalid" -- so that no peer waits for them)
+  const bool met = sh.fail == DSYNC_OK;
+  const uint64_t epoch = sh.epoch;
+  __syncthreads();
+  if (t < n) {
+    DsyncPage* mine = a.d.page[me];
+    uint64_t sc = ld_sys64(a.sendcounts + t), rc = ld_sys64(a.recvcaps + t);
+    const uint64_t sd = ld_sys64(a.sdispls + t), rd = ld_sys64(a.rdispls + t);
+    const bool row_ok = met && sd <= a.send_extent && sc <= a.send_extent - sd && rd <= a.recv_extent && rc <= a.recv_extent - rd;
+    if (!row_ok) sc = rc = 0;
+    if (met && !row_ok) atomicMax(&vs.bounds, (uint32_t)(kDsyncRanks - t));
+    if (blockIdx.x == 0) {  // one block posts this rank's boxes (the own pair goes through its own page, by the same rules)
+      VBox* out = vbox_of(a.d.page[t]) + me;
+      st_sys64(&out->count, sc);
+      st_sys64(&out->rdispl, rd);
+      st_sys64(&out->cap, rc);
+      st_sys64(&out->valid, row_ok ? 1u : 0u);
+      __hip_atomic_store(&out->epoch, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    uint64_t moved = 0, to = 0;
+    if (met) {
+      const VBox* in = vbox_of(mine) + t;
+      const uint32_t why = dsync_spin(&in->epoch, epoch, a.d);
+      if (why == DSYNC_OK) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        const uint64_t in_count = ld_sys64(&in->count), in_rd = ld_sys64(&in->rdispl), in_cap = ld_sys64(&in->cap);
+        const bool pair = row_ok && ld_sys64(&in->valid) != 0;
+        if (blockIdx.x == 0) st_sys64(a.recvcounts + t, in_count);
+        if (pair) {
+          if (sc > in_cap || in_count > rc) atomicMax(&vs.trunc, (uint32_t)(kDsyncRanks - t));
+          if (sc <= in_cap) {  // (the peer checked in_rd + in_cap against ITS extent)
+            moved = sc;
+            to = sh.recv[t] + in_rd * ES;
+          }
+        }
+      } else {
+        atomicMax(&sh.fail, why);
+      }
+    }
+    const int d = (t - me + n) % n;
+    vs.src[d] = sh.send[me] + sd * ES;
+    vs.dst[d] = to;
+    vs.bytes[d] = moved * ES;
+  }
+  __syncthreads();
+  if (t == 0) {
+    uint64_t tiles = 0;
+    for (int d = 0; d < n; d++) {
+      vs.tile0[d] = tiles;
+      const uint64_t bytes = vs.bytes[d];
+      if (bytes == 0) continue;
+      if (((vs.src[d] ^ vs.dst[d]) & 15u) == 0) {
+        const uint64_t head = (16u - (vs.src[d] & 15u)) & 15u, npack = bytes > head ? (bytes - head) / 16 : 0;
+        tiles += npack > kVTile ? (npack + kVTile - 1) / kVTile : 1;
+      } else {
+        tiles += (bytes / ES + kVTile - 1) / kVTile;
+      }
+    }
+    vs.tile0[n] = tiles;
+    const uint32_t bounds = vs.bounds, trunc = vs.trunc;
+    if (blockIdx.x == 0 && a.vstatus && (bounds | trunc))
+      __hip_atomic_store(a.vstatus, bounds ? (uint32_t)DSYNC_BOUNDS | ((kDsyncRanks - bounds + 1u) << 8) : (uint32_t)DSYNC_TRUNCATE | ((kDsyncRanks - trunc + 1u) << 8),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  __syncthreads();
+  if (sh.fail == DSYNC_OK) {
+    const uint64_t total = vs.tile0[n];
+    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+      int d = 0;
+#pragma unroll
+      for (int k = 1; k < kDsyncRanks; k++)
+        if (k < n && tile >= vs.tile0[k]) d = k;
+      const uint64_t k = tile - vs.tile0[d], bytes = vs.bytes[d];
+      const char* src = reinterpret_cast<const char*>(uniform64(vs.src[d]));
+      char* dst = reinterpret_cast<char*>(uniform64(vs.dst[d]));
+      if ((((uintptr_t)src ^ (uintptr_t)dst) & 15u) == 0) {
+        const uint64_t lead = (16u - ((uintptr_t)src & 15u)) & 15u, head = lead < bytes ? lead : bytes, npack = (bytes - head) / 16;
+        const pack_t* ps = reinterpret_cast<const pack_t*>(src + head);
+        pack_t* pd = reinterpret_cast<pack_t*>(dst + head);
+        const uint64_t base = k * kVTile;
+        if (base + kVTile <= npack) {
+          pack_t v[kUnroll];
+#pragma unroll
+          for (int u = 0; u < kUnroll; u++) v[u] = ldp<2>(ps + base + (size_t)u * kBlock + t);
+#pragma unroll
+          for (int u = 0; u < kUnroll; u++) stp<1>(pd + base + (size_t)u * kBlock + t, v[u]);
+        } else {
+          for (int u = 0; u < kUnroll; u++) {
+            const uint64_t i = base + (size_t)u * kBlock + t;
+            if (i >= npack) break;
+            stp<1>(pd + i, ldp<2>(ps + i));
+          }
+        }
+        if (k == 0) {  // the ragged ends (< 16 bytes each): the first lanes of the segment's first tile
+          const uint64_t tail = head + npack * 16;
+          if ((uint64_t)t < head) __builtin_nontemporal_store(__builtin_nontemporal_load(src + t), dst + t);
+          if (tail + t < bytes) __builtin_nontemporal_store(__builtin_nontemporal_load(src + tail + t), dst + tail + t);
+        }
+      } else {  // source and destination differ mod 16: one element per lane
+        typedef typename VElem<ES>::type E;
+        const uint64_t count = bytes / ES;
+        for (int u = 0; u < kUnroll; u++) {
+          const uint64_t i = k * kVTile + (size_t)u * kBlock + t;
+          if (i >= count) break;
+          __builtin_nontemporal_store(__builtin_nontemporal_load(reinterpret_cast<const E*>(src) + i), reinterpret_cast<E*>(dst) + i);
+        }
+      }
+    }
+  }
+  dsync_end(a.d, sh);
+}
+
 // ---- launch helpers --------------------------------------------------------------------------
 
 // plain launch, or a launch that carries its own begin / end events
@@ -1311,6 +1453,19 @@ hipError_t launch_dsync_fold(const DsyncArgs& a, int nsrc, int dtype, int op, in
     case DT_BF16: return dsync_typed<bf16_t>(a, nsrc, op, grid_x, unroll, s, es, ee);
     default: return hipErrorInvalidValue;
   }
+}
+
+hipError_t launch_dsync_alltoallv(const DsyncVArgs& a, int elem_size, int grid_x, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
+  if (a.d.n < 1 || a.d.n > kDsyncRanks || !a.sendcounts || !a.sdispls || !a.recvcaps || !a.rdispls || !a.recvcounts) return hipErrorInvalidValue;
+  const dim3 grid(grid_x < 1 ? 1 : grid_x);
+  switch (elem_size) {
+    case 1: XMPI_LAUNCH((dsync_alltoallv_kernel<1>), grid, dim3(kBlock), s, es, ee, a); break;
+    case 2: XMPI_LAUNCH((dsync_alltoallv_kernel<2>), grid, dim3(kBlock), s, es, ee, a); break;
+    case 4: XMPI_LAUNCH((dsync_alltoallv_kernel<4>), grid, dim3(kBlock), s, es, ee, a); break;
+    case 8: XMPI_LAUNCH((dsync_alltoallv_kernel<8>), grid, dim3(kBlock), s, es, ee, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 }  // namespace xmpi

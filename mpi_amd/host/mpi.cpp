@@ -126,6 +126,15 @@ Error Alltoall(const Data& send, Data recv) {
   Collective* c = collective_or_null();
   return c ? c->Alltoall(send, recv) : no_collectives();
 }
+Error Alltoallv(const Data& send, const std::vector<uint64_t>& sendcounts, const std::vector<uint64_t>& sdispls, Data recv,
+                const std::vector<uint64_t>& recvcaps, const std::vector<uint64_t>& rdispls, std::vector<uint64_t>* recvcounts) {
+  Collective* c = collective_or_null();
+  return c ? c->Alltoallv(send, sendcounts, sdispls, recv, recvcaps, rdispls, recvcounts) : no_collectives();
+}
+Error Collective::Alltoallv(const Data&, const std::vector<uint64_t>&, const std::vector<uint64_t>&, Data, const std::vector<uint64_t>&,
+                            const std::vector<uint64_t>&, std::vector<uint64_t>*) {
+  return Error(XMPI_ERR_UNSUPPORTED, "mpi alltoallv: unsupported by this backend");
+}
 // (a backend that has the four older collectives need not have these two)
 Error Collective::ReduceScatter(const Data&, Data, xmpi_op) { return Error(XMPI_ERR_UNSUPPORTED, "mpi reduce_scatter: unsupported by this backend"); }
 Error Collective::Alltoall(const Data&, Data) { return Error(XMPI_ERR_UNSUPPORTED, "mpi alltoall: unsupported by this backend"); }
@@ -256,6 +265,22 @@ Error XGMI::Alltoall(const Data& send, Data recv) {
   if (Error err = blocks_of(send, Size(), &block, "mpi alltoall")) return err;
   if (recv.resize) recv.resize(recv.owner, send.count, &recv);
   return from_code(xmpi_alltoall(comm_, send.ptr, recv.ptr, block, send.dtype, personal_algo(Algo, false)), "mpi alltoall");
+}
+
+Error XGMI::Alltoallv(const Data& send, const std::vector<uint64_t>& sendcounts, const std::vector<uint64_t>& sdispls, Data recv,
+                      const std::vector<uint64_t>& recvcaps, const std::vector<uint64_t>& rdispls, std::vector<uint64_t>* recvcounts) {
+  const size_t n = (size_t)Size();
+  if (sendcounts.size() != n || sdispls.size() != n || recvcaps.size() != n || rdispls.size() != n || !recvcounts)
+    return Error(XMPI_ERR_ARG, "mpi alltoallv: the arrays have one entry per rank");
+  if (recv.resize) {  // every slot fits: what lies between the slots is the container's own (new elements: zero)
+    size_t extent = 0;
+    for (size_t r = 0; r < n; r++) extent = std::max<size_t>(extent, (size_t)(rdispls[r] + recvcaps[r]));
+    recv.resize(recv.owner, extent, &recv);
+  }
+  recvcounts->assign(n, 0);
+  const int algo = Algo == XMPI_ALGO_ZCOPY || Algo == XMPI_ALGO_DIRECT ? Algo : (int)XMPI_ALGO_AUTO;
+  return from_code(xmpi_alltoallv(comm_, send.ptr, send.count, sendcounts.data(), sdispls.data(), recv.ptr, recv.count, recvcaps.data(),
+                                  rdispls.data(), recvcounts->data(), send.dtype, algo), "mpi alltoallv");
 }
 
 Error XGMI::Barrier() { return from_code(xmpi_barrier(comm_), "mpi barrier"); }

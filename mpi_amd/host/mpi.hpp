@@ -120,6 +120,12 @@ class Collective {
   // recv (Size() blocks) = block `me` of rank 0, of rank 1, ...  A backend that does not have them says so.
   virtual Error ReduceScatter(const Data& send, Data recv, xmpi_op op);
   virtual Error Alltoall(const Data& send, Data recv);
+  // The exchange helloworld.go:53-81 really performs: a count per pair, the receiver learning it (network.go:594-601).  All in
+  // elements of send's type: sendcounts[j] elements from send + sdispls[j] go to rank j; what rank r sends lands at recv + rdispls[r]
+  // if it is at most recvcaps[r] elements; *recvcounts = what every rank sent.  A destination made by Into() is re-sized to hold
+  // every slot (max of rdispls[r] + recvcaps[r]) before the call.
+  virtual Error Alltoallv(const Data& send, const std::vector<uint64_t>& sendcounts, const std::vector<uint64_t>& sdispls, Data recv,
+                          const std::vector<uint64_t>& recvcaps, const std::vector<uint64_t>& rdispls, std::vector<uint64_t>* recvcounts);
 };
 
 // flags.go:10-14
@@ -149,6 +155,8 @@ Error Allreduce(const Data& send, Data recv, xmpi_op op = XMPI_SUM);
 Error Allgather(const Data& send, Data recv);
 Error ReduceScatter(const Data& send, Data recv, xmpi_op op = XMPI_SUM);
 Error Alltoall(const Data& send, Data recv);
+Error Alltoallv(const Data& send, const std::vector<uint64_t>& sendcounts, const std::vector<uint64_t>& sdispls, Data recv,
+                const std::vector<uint64_t>& recvcaps, const std::vector<uint64_t>& rdispls, std::vector<uint64_t>* recvcounts);
 Error Barrier();
 
 // The MI355X backend: replaces type Network (network.go:25-39).  Zero-valued fields are taken from
@@ -175,6 +183,8 @@ class XGMI : public Interface, public Collective {
   Error Allgather(const Data& send, Data recv) override;
   Error ReduceScatter(const Data& send, Data recv, xmpi_op op) override;
   Error Alltoall(const Data& send, Data recv) override;
+  Error Alltoallv(const Data& send, const std::vector<uint64_t>& sendcounts, const std::vector<uint64_t>& sdispls, Data recv,
+                  const std::vector<uint64_t>& recvcaps, const std::vector<uint64_t>& rdispls, std::vector<uint64_t>* recvcounts) override;
   Error Barrier() override;
 
   // The Send / Wait pair the reference sketches in a comment (mpi.go:132-152): SendNoWait returns once

@@ -57,6 +57,9 @@ SYMBOLS = [
     ("xmpi_allgather", _I, [_P, _P, _P, _Z, _I, _I]),
     ("xmpi_reduce_scatter", _I, [_P, _P, _P, _Z, _I, _I, _I]),
     ("xmpi_alltoall", _I, [_P, _P, _P, _Z, _I, _I]),
+    ("xmpi_alltoallv", _I, [_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _P, _I, _I]),
+    ("xmpi_alltoallv_on_stream", _I, [_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _P, _I, _P]),
+    ("xmpi_alltoallv_partner", _I, [_I, _I, _I]),
     ("xmpi_reduce_local", _I, [_P, _P, _P, _P, _Z, _I, _I]),
     ("xmpi_reduce_local_n", _I, [_P, _P, C.POINTER(_P), _I, _Z, _I, _I]),
     ("xmpi_copy_local", _I, [_P, _P, _P, _Z]),
@@ -402,6 +405,32 @@ class Comm:
     def alltoall(self, send, recv, count: int, dtype: int, algo: int = ALGO_AUTO) -> None:
         """recv[r*count:(r+1)*count] = rank r's send[me*count:(me+1)*count]; count = elements per block"""
         _check(lib().xmpi_alltoall(self.handle, _ptr(send), _ptr(recv), count, dtype, algo), "xmpi_alltoall")
+
+    def alltoallv(self, send, send_extent: int, sendcounts, sdispls, recv, recv_extent: int, recvcaps, rdispls,
+                  dtype: int, algo: int = ALGO_AUTO) -> np.ndarray:
+        """an all-to-all with a count per pair (elements of dtype everywhere): sendcounts[j] elements from send + sdispls[j] go to
+        rank j, what rank r sends lands at recv + rdispls[r] if it is at most recvcaps[r] elements.  Returns the counts received
+        (also of blocks that were too long).  A truncated pair or a row out of its extents raises XmpiError AFTER every other
+        block has been delivered; the counts received are then in the exception's `recvcounts`."""
+        n = self.size()
+        arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (sendcounts, sdispls, recvcaps, rdispls)]
+        if any(a.shape != (n,) for a in arrs):
+            raise XmpiError(ERR_ARG, "xmpi_alltoallv", "the arrays have one entry per rank")
+        got = np.zeros(n, dtype=np.uint64)
+        rc = lib().xmpi_alltoallv(self.handle, _ptr(send), send_extent, arrs[0].ctypes.data, arrs[1].ctypes.data, _ptr(recv), recv_extent,
+                                  arrs[2].ctypes.data, arrs[3].ctypes.data, got.ctypes.data, dtype, algo)
+        if rc != OK:
+            err = XmpiError(rc, "xmpi_alltoallv", lib().xmpi_last_error().decode(errors="replace"))
+            err.recvcounts = got
+            raise err
+        return got
+
+    def alltoallv_on_stream(self, send, send_extent: int, sendcounts, sdispls, recv, recv_extent: int, recvcaps, rdispls, recvcounts,
+                            dtype: int, stream=None) -> None:
+        """the stream-ordered form: the five arrays are memory the DEVICE addresses (DeviceBuffers of uint64, one entry per rank),
+        read and written when the kernel runs"""
+        _check(lib().xmpi_alltoallv_on_stream(self.handle, _ptr(send), send_extent, _ptr(sendcounts), _ptr(sdispls), _ptr(recv), recv_extent,
+                                              _ptr(recvcaps), _ptr(rdispls), _ptr(recvcounts), dtype, stream), "xmpi_alltoallv_on_stream")
 
     def reduce_scatter_on_stream(self, send, recv, count: int, dtype: int, op: int, stream=None) -> None:
         _check(lib().xmpi_reduce_scatter_on_stream(self.handle, _ptr(send), _ptr(recv), count, dtype, op, stream),

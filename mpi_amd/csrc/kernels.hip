@@ -17,8 +17,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "../../include/xmpi.h"
 #include "kdev.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace xmpi {
 namespace {
@@ -890,146 +892,74 @@ __global__ __launch_bounds__(kBlock) void dsync_alltoallv_kernel(DsyncVArgs a) {
   dsync_end(a.d, sh);
 }
 
-// ---- launch helpers --------------------------------------------------------------------------
-
-// plain launch, or a launch that carries its own begin / end events
-#define XMPI_LAUNCH(kern, grid, block, stream, es, ee, ...)                                  \
-  do {                                                                                       \
-    if ((es) || (ee)) hipExtLaunchKernelGGL(kern, grid, block, 0, stream, es, ee, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);                      \
-  } while (0)
+// ---- launchers (dispatch helpers: launch.h) -----------------------------------------------------
 
 int g_kernel_mode = -1;   // -1 = by size, else forced 0 / 1 / 2
-// 0 = one tile per block, the hardware dispatcher balances (measured better than a 2048-block
-// grid-stride loop inside the collective: reduce_n 60 -> 56 us per 288 MiB); > 0 caps the grid
-int g_grid_cap = 0;
+int g_grid_cap = 0;       // 0 = one tile per block, > 0 caps the grid (launch.h grid_for)
 
-inline int kernel_mode_for(size_t traffic_bytes) {
-  if (g_kernel_mode >= 0) return g_kernel_mode;
-  // a launch whose traffic exceeds what the caches can hold streams through them: keep its loads
-  // from displacing anything (nt); small launches are served from L2 / Infinity Cache as they are
-  return traffic_bytes >= (size_t)(48u << 20) ? 2 : 0;
+// the batch launchers' grid: x covers the longest segment, a grid cap is shared out among the n segments
+inline int batch_grid_x(size_t max_packets, int n) {
+  int gx = grid_for(max_packets + 1, (size_t)kBlock * kUnroll);
+  const int cap = g_grid_cap > 0 ? (g_grid_cap + n - 1) / n : 0;
+  return cap > 0 && gx > cap ? cap : gx;
 }
 
-inline int grid_for(size_t work_items, size_t per_block) {
-  size_t g = (work_items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g_grid_cap > 0 && g > (size_t)g_grid_cap) g = (size_t)g_grid_cap;
-  if (g > 0x7fffffffu) g = 0x7fffffffu;
-  return (int)g;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-template <typename T, int OP>
-hipError_t reduce2_typed(void* dst, const void* a, const void* b, size_t count, hipStream_t s, hipEvent_t es,
-                         hipEvent_t ee) {
-  if (aligned16(dst) && aligned16(a) && aligned16(b)) {
-    constexpr size_t N = 16 / sizeof(T);
-    const size_t npack = count / N;
-    const int grid = grid_for(npack, (size_t)kBlock * kUnroll);
-    const int mode = kernel_mode_for(3 * count * sizeof(T));
-    if (mode == 1)
-      XMPI_LAUNCH((reduce2_kernel<T, OP, 1>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a, (const T*)b,
-                  npack, count);
-    else if (mode == 2)
-      XMPI_LAUNCH((reduce2_kernel<T, OP, 2>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a, (const T*)b,
-                  npack, count);
-    else
-      XMPI_LAUNCH((reduce2_kernel<T, OP, 0>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a, (const T*)b,
-                  npack, count);
-  } else {
-    const int grid = grid_for(count, kBlock);
-    XMPI_LAUNCH((reduce2_elem_kernel<T, OP>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a,
-                (const T*)b, count);
+// The batch launchers without their batch kernel: one plain launch per destination there IS, in the order i = 0 .. n-1 and, within
+// a segment, which = 0 then 1.  `dest(i, which)` is that destination, or null where there is nothing to launch; `launch(i, d, es, ee)`
+// launches segment i into d.  The events ride on the first and on the last launch; nothing launched: still honoured.
+template <typename Dest, typename Launch>
+hipError_t launch_per_dest(int n, hipStream_t s, hipEvent_t es, hipEvent_t ee, Dest&& dest, Launch&& launch) {
+  int nlaunch = 0, k = 0;
+  for (int j = 0; j < 2 * n; j++) nlaunch += dest(j / 2, j % 2) != nullptr;
+  for (int j = 0; j < 2 * n; j++) {
+    void* d = dest(j / 2, j % 2);
+    if (!d) continue;
+    hipError_t e = launch(j / 2, d, k == 0 ? es : nullptr, k == nlaunch - 1 ? ee : nullptr);
+    if (e != hipSuccess) return e;
+    k++;
   }
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t reduce2_op(void* dst, const void* a, const void* b, size_t count, int op, hipStream_t s, hipEvent_t es,
-                      hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: return reduce2_typed<T, OP_SUM>(dst, a, b, count, s, es, ee);
-    case OP_PROD: return reduce2_typed<T, OP_PROD>(dst, a, b, count, s, es, ee);
-    case OP_MIN: return reduce2_typed<T, OP_MIN>(dst, a, b, count, s, es, ee);
-    case OP_MAX: return reduce2_typed<T, OP_MAX>(dst, a, b, count, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename T, int OP>
-hipError_t reduce_n_typed(void* dst, const SrcPtrs& srcs, int nsrc, size_t count, hipStream_t s, hipEvent_t es,
-                          hipEvent_t ee) {
-  constexpr size_t N = 16 / sizeof(T);
-  const size_t npack = count / N;
-  const int grid = grid_for(npack, kBlock);
-  const int mode = kernel_mode_for((size_t)(nsrc + 1) * count * sizeof(T));
-#define XMPI_RN(NS)                                                                                            \
-  case NS:                                                                                                     \
-    if (mode != 0)                                                                                             \
-      XMPI_LAUNCH((reduce_n_kernel<T, OP, NS, 2>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, srcs, nsrc, npack, \
-                  count);                                                                                      \
-    else                                                                                                       \
-      XMPI_LAUNCH((reduce_n_kernel<T, OP, NS, 0>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, srcs, nsrc, npack, \
-                  count);                                                                                      \
-    break;
-  switch (nsrc) {
-    XMPI_RN(2) XMPI_RN(3) XMPI_RN(4) XMPI_RN(5) XMPI_RN(6) XMPI_RN(7) XMPI_RN(8)
-    default:
-      XMPI_LAUNCH((reduce_n_kernel<T, OP, 0, 0>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, srcs, nsrc, npack,
-                  count);
-      break;
-  }
-#undef XMPI_RN
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t reduce_n_op(void* dst, const SrcPtrs& srcs, int nsrc, size_t count, int op, hipStream_t s, hipEvent_t es,
-                       hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: return reduce_n_typed<T, OP_SUM>(dst, srcs, nsrc, count, s, es, ee);
-    case OP_PROD: return reduce_n_typed<T, OP_PROD>(dst, srcs, nsrc, count, s, es, ee);
-    case OP_MIN: return reduce_n_typed<T, OP_MIN>(dst, srcs, nsrc, count, s, es, ee);
-    case OP_MAX: return reduce_n_typed<T, OP_MAX>(dst, srcs, nsrc, count, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  if (nlaunch == 0) record_events(es, ee, s);
+  return hipSuccess;
 }
 
 }  // namespace
 
 hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count, int dtype, int op,
                           hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  if (count == 0) {  // nothing to launch: still honour the events
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+  if (count == 0) {
+    record_events(es, ee, s);
     return hipSuccess;
   }
-  switch (dtype) {
-    case DT_U8: return reduce2_op<uint8_t>(dst, a, b, count, op, s, es, ee);
-    case DT_I32: return reduce2_op<int32_t>(dst, a, b, count, op, s, es, ee);
-    case DT_I64: return reduce2_op<int64_t>(dst, a, b, count, op, s, es, ee);
-    case DT_F16: return reduce2_op<_Float16>(dst, a, b, count, op, s, es, ee);
-    case DT_F32: return reduce2_op<float>(dst, a, b, count, op, s, es, ee);
-    case DT_F64: return reduce2_op<double>(dst, a, b, count, op, s, es, ee);
-    case DT_BF16: return reduce2_op<bf16_t>(dst, a, b, count, op, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      if (aligned16(dst) && aligned16(a) && aligned16(b)) {
+        const size_t npack = count / (16 / sizeof(T));
+        const int grid = grid_for(npack, (size_t)kBlock * kUnroll);
+        return with_mode012(kernel_mode_for(3 * count * sizeof(T)), [&](auto m) {
+          XMPI_LAUNCH((reduce2_kernel<T, OP, decltype(m)::value>), dim3(grid), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a,
+                      (const T*)b, npack, count);
+          return hipGetLastError();
+        });
+      }
+      XMPI_LAUNCH((reduce2_elem_kernel<T, OP>), dim3(grid_for(count, kBlock)), dim3(kBlock), s, es, ee, (T*)dst, (const T*)a,
+                  (const T*)b, count);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_reduce_n(void* dst, const void* const* srcs, int nsrc, size_t count, int dtype,
                            int op, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
   if (nsrc < 1 || nsrc > kMaxReduceSrcs) return hipErrorInvalidValue;
-  if (count == 0) {  // nothing to launch: still honour the events
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+  if (count == 0) {
+    record_events(es, ee, s);
     return hipSuccess;
   }
   if (nsrc == 1) {
-    static const size_t esz[] = {1, 4, 8, 2, 4, 8, 2};
-    if (dtype < 0 || dtype > DT_BF16) return hipErrorInvalidValue;
-    return launch_copy(dst, srcs[0], count * esz[dtype], s, es, ee);
+    const size_t esz = xmpi_dtype_size((xmpi_dtype)dtype);
+    return esz ? launch_copy(dst, srcs[0], count * esz, s, es, ee) : hipErrorInvalidValue;
   }
   bool ok = aligned16(dst);
   SrcPtrs p;
@@ -1039,68 +969,38 @@ hipError_t launch_reduce_n(void* dst, const void* const* srcs, int nsrc, size_t 
     void* d1[1] = {dst};
     return launch_reduce_n_multi(d1, 1, srcs, nsrc, count, dtype, op, s, es, ee);
   }
-  switch (dtype) {
-    case DT_U8: return reduce_n_op<uint8_t>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_I32: return reduce_n_op<int32_t>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_I64: return reduce_n_op<int64_t>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_F16: return reduce_n_op<_Float16>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_F32: return reduce_n_op<float>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_F64: return reduce_n_op<double>(dst, p, nsrc, count, op, s, es, ee);
-    case DT_BF16: return reduce_n_op<bf16_t>(dst, p, nsrc, count, op, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      const size_t npack = count / (16 / sizeof(T));
+      const int grid = grid_for(npack, kBlock);
+      const int mode = kernel_mode_for((size_t)(nsrc + 1) * count * sizeof(T));
+      return with_nsrc_mode<2, 3, 4, 5, 6, 7, 8>(nsrc, mode, [&](auto ns, auto m) {
+        XMPI_LAUNCH((reduce_n_kernel<T, decltype(o)::value, decltype(ns)::value, decltype(m)::value>), dim3(grid), dim3(kBlock), s,
+                    es, ee, (T*)dst, p, nsrc, npack, count);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_copy(void* dst, const void* src, size_t bytes, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  if (bytes == 0 || dst == src) {  // nothing to launch: still honour the events
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+  if (bytes == 0 || dst == src) {
+    record_events(es, ee, s);
     return hipSuccess;
   }
   if (aligned16(dst) && aligned16(src)) {
     const size_t npack = bytes / 16;
     const int grid = grid_for(npack, (size_t)kBlock * kUnroll);
-    const int mode = kernel_mode_for(2 * bytes);
-    if (mode == 1)
-      XMPI_LAUNCH(copy16_kernel<1>, dim3(grid), dim3(kBlock), s, es, ee, (pack_t*)dst, (const pack_t*)src, npack, bytes);
-    else if (mode == 2)
-      XMPI_LAUNCH(copy16_kernel<2>, dim3(grid), dim3(kBlock), s, es, ee, (pack_t*)dst, (const pack_t*)src, npack, bytes);
-    else
-      XMPI_LAUNCH(copy16_kernel<0>, dim3(grid), dim3(kBlock), s, es, ee, (pack_t*)dst, (const pack_t*)src, npack, bytes);
-  } else {
-    XMPI_LAUNCH(copy1_kernel, dim3(grid_for(bytes, kBlock)), dim3(kBlock), s, es, ee, (uint8_t*)dst,
-                (const uint8_t*)src, bytes);
+    return with_mode012(kernel_mode_for(2 * bytes), [&](auto m) {
+      XMPI_LAUNCH((copy16_kernel<decltype(m)::value>), dim3(grid), dim3(kBlock), s, es, ee, (pack_t*)dst, (const pack_t*)src, npack,
+                  bytes);
+      return hipGetLastError();
+    });
   }
+  XMPI_LAUNCH(copy1_kernel, dim3(grid_for(bytes, kBlock)), dim3(kBlock), s, es, ee, (uint8_t*)dst, (const uint8_t*)src, bytes);
   return hipGetLastError();
 }
-
-namespace {
-template <typename T, int OP>
-hipError_t reduce2_batch_typed(const Reduce2Batch& q, int n, size_t maxcount, size_t total, hipStream_t s,
-                               hipEvent_t es, hipEvent_t ee) {
-  constexpr size_t N = 16 / sizeof(T);
-  int gx = grid_for(maxcount / N + 1, (size_t)kBlock * kUnroll);
-  const int cap = g_grid_cap > 0 ? (g_grid_cap + n - 1) / n : 0;
-  if (cap > 0 && gx > cap) gx = cap;
-  const int mode = kernel_mode_for(3 * total * sizeof(T));
-  if (mode == 1) XMPI_LAUNCH((reduce2_batch_kernel<T, OP, 1>), dim3(gx, n), dim3(kBlock), s, es, ee, q);
-  else if (mode == 2) XMPI_LAUNCH((reduce2_batch_kernel<T, OP, 2>), dim3(gx, n), dim3(kBlock), s, es, ee, q);
-  else XMPI_LAUNCH((reduce2_batch_kernel<T, OP, 0>), dim3(gx, n), dim3(kBlock), s, es, ee, q);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t reduce2_batch_op(const Reduce2Batch& q, int n, size_t maxcount, size_t total, int op, hipStream_t s,
-                            hipEvent_t es, hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: return reduce2_batch_typed<T, OP_SUM>(q, n, maxcount, total, s, es, ee);
-    case OP_PROD: return reduce2_batch_typed<T, OP_PROD>(q, n, maxcount, total, s, es, ee);
-    case OP_MIN: return reduce2_batch_typed<T, OP_MIN>(q, n, maxcount, total, s, es, ee);
-    case OP_MAX: return reduce2_batch_typed<T, OP_MAX>(q, n, maxcount, total, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
-}
-}  // namespace
 
 hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void* const* a, const void* const* b,
                                 const size_t* counts, int n, int dtype, int op, hipStream_t s, hipEvent_t es,
@@ -1120,39 +1020,22 @@ hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void*
     fused = fused || q.dst2[i] != nullptr || dst[i] == nullptr;
     ok = ok && aligned16(dst[i]) && aligned16(q.dst2[i]) && aligned16(a[i]) && aligned16(b[i]);
   }
-  if (!ok || (n == 1 && !fused) || maxc == 0) {  // odd alignment / nothing to fuse: plain launches
-    // The local destination may alias an operand (in-place ring step: dst == a): the forwarded copy is
-    // computed FIRST, from the untouched operands, and the aliasing store comes last.  The events ride on the first
-    // and the last launch there IS: a segment without elements or without a destination launches nothing.
-    int nlaunch = 0;
-    for (int i = 0; i < n; i++)
-      if (counts[i] > 0) nlaunch += (q.dst2[i] != nullptr) + (dst[i] != nullptr);
-    int k = 0;
-    for (int i = 0; i < n; i++)
-      for (int w = 0; w < 2; w++) {
-        void* d = w == 0 ? q.dst2[i] : dst[i];
-        if (!d || counts[i] == 0) continue;
-        hipError_t e = launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, k == 0 ? es : nullptr,
-                                      k == nlaunch - 1 ? ee : nullptr);
-        if (e != hipSuccess) return e;
-        k++;
-      }
-    if (nlaunch == 0) {  // nothing launched: still honour the events
-      if (es) (void)hipEventRecord(es, s);
-      if (ee) (void)hipEventRecord(ee, s);
-    }
-    return hipSuccess;
-  }
-  switch (dtype) {
-    case DT_U8: return reduce2_batch_op<uint8_t>(q, n, maxc, total, op, s, es, ee);
-    case DT_I32: return reduce2_batch_op<int32_t>(q, n, maxc, total, op, s, es, ee);
-    case DT_I64: return reduce2_batch_op<int64_t>(q, n, maxc, total, op, s, es, ee);
-    case DT_F16: return reduce2_batch_op<_Float16>(q, n, maxc, total, op, s, es, ee);
-    case DT_F32: return reduce2_batch_op<float>(q, n, maxc, total, op, s, es, ee);
-    case DT_F64: return reduce2_batch_op<double>(q, n, maxc, total, op, s, es, ee);
-    case DT_BF16: return reduce2_batch_op<bf16_t>(q, n, maxc, total, op, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  if (!ok || (n == 1 && !fused) || maxc == 0)  // odd alignment / nothing to fuse: plain launches
+    // The local destination may alias an operand (in-place ring step: dst == a): the forwarded copy is computed FIRST, from the
+    // untouched operands, and the aliasing store comes last.  A segment without elements or without a destination launches nothing.
+    return launch_per_dest(
+        n, s, es, ee, [&](int i, int which) { return counts[i] == 0 ? nullptr : which == 0 ? q.dst2[i] : dst[i]; },
+        [&](int i, void* d, hipEvent_t e0, hipEvent_t e1) { return launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, e0, e1); });
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      const dim3 grid(batch_grid_x(maxc / (16 / sizeof(T)), n), n);
+      return with_mode012(kernel_mode_for(3 * total * sizeof(T)), [&](auto m) {
+        XMPI_LAUNCH((reduce2_batch_kernel<T, decltype(o)::value, decltype(m)::value>), grid, dim3(kBlock), s, es, ee, q);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_copy_batch(void* const* dst, void* const* dst2, const void* const* src, const size_t* bytes, int n,
@@ -1171,93 +1054,30 @@ hipError_t launch_copy_batch(void* const* dst, void* const* dst2, const void* co
     fused = fused || b.dst2[i] != nullptr;
     ok = ok && aligned16(dst[i]) && aligned16(b.dst2[i]) && aligned16(src[i]);
   }
-  if (!ok || (n == 1 && !fused)) {  // odd alignment: one launch per copy, the events span the group (as launch_reduce2_batch:
-    // on the first and the last launch there is)
-    int nlaunch = 0;
-    for (int i = 0; i < n; i++)
-      if (bytes[i] > 0) nlaunch += (dst[i] && dst[i] != src[i]) + (b.dst2[i] && b.dst2[i] != src[i]);
-    int k = 0;
-    for (int i = 0; i < n; i++)
-      for (int w = 0; w < 2; w++) {
-        void* d = w == 0 ? dst[i] : b.dst2[i];
-        if (!d || d == src[i] || bytes[i] == 0) continue;
-        hipError_t e = launch_copy(d, src[i], bytes[i], s, k == 0 ? es : nullptr, k == nlaunch - 1 ? ee : nullptr);
-        if (e != hipSuccess) return e;
-        k++;
-      }
-    if (nlaunch == 0) {  // nothing launched: still honour the events
-      if (es) (void)hipEventRecord(es, s);
-      if (ee) (void)hipEventRecord(ee, s);
-    }
-    return hipSuccess;
-  }
+  if (!ok || (n == 1 && !fused))  // odd alignment: one launch per copy that moves anything, dst then dst2
+    return launch_per_dest(
+        n, s, es, ee,
+        [&](int i, int which) {
+          void* d = which == 0 ? dst[i] : b.dst2[i];
+          return bytes[i] == 0 || d == src[i] ? nullptr : d;
+        },
+        [&](int i, void* d, hipEvent_t e0, hipEvent_t e1) { return launch_copy(d, src[i], bytes[i], s, e0, e1); });
   if (maxb == 0) {
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+    record_events(es, ee, s);
     return hipSuccess;
   }
-  int gx = grid_for(maxb / 16 + 1, (size_t)kBlock * kUnroll);
-  const int cap = g_grid_cap > 0 ? (g_grid_cap + n - 1) / n : 0;
-  if (cap > 0 && gx > cap) gx = cap;
-  const int mode = kernel_mode_for(2 * total);
-  if (mode == 1) XMPI_LAUNCH(copy_batch_kernel<1>, dim3(gx, n), dim3(kBlock), s, es, ee, b);
-  else if (mode == 2) XMPI_LAUNCH(copy_batch_kernel<2>, dim3(gx, n), dim3(kBlock), s, es, ee, b);
-  else XMPI_LAUNCH(copy_batch_kernel<0>, dim3(gx, n), dim3(kBlock), s, es, ee, b);
-  return hipGetLastError();
-}
-
-namespace {
-template <typename T, int OP>
-hipError_t reduce_n_multi_typed(const MultiPtrs& q, int nsrc, int ndst, size_t count, bool vec, hipStream_t s,
-                                hipEvent_t es, hipEvent_t ee) {
-  if (!vec) {
-    XMPI_LAUNCH((reduce_n_multi_elem_kernel<T, OP>), dim3(grid_for(count, kBlock)), dim3(kBlock), s, es, ee, q, nsrc,
-                ndst, count);
+  const dim3 grid(batch_grid_x(maxb / 16, n), n);
+  return with_mode012(kernel_mode_for(2 * total), [&](auto m) {
+    XMPI_LAUNCH((copy_batch_kernel<decltype(m)::value>), grid, dim3(kBlock), s, es, ee, b);
     return hipGetLastError();
-  }
-  constexpr size_t N = 16 / sizeof(T);
-  const size_t npack = count / N;
-  const int grid = grid_for(npack, kBlock);
-  const int mode = kernel_mode_for((size_t)(nsrc + ndst) * count * sizeof(T));
-#define XMPI_RNM(NS)                                                                                              \
-  case NS:                                                                                                        \
-    if (mode != 0)                                                                                                \
-      XMPI_LAUNCH((reduce_n_multi_kernel<T, OP, NS, 2>), dim3(grid), dim3(kBlock), s, es, ee, q, nsrc, ndst, npack, \
-                  count);                                                                                         \
-    else                                                                                                          \
-      XMPI_LAUNCH((reduce_n_multi_kernel<T, OP, NS, 0>), dim3(grid), dim3(kBlock), s, es, ee, q, nsrc, ndst, npack, \
-                  count);                                                                                         \
-    break;
-  switch (nsrc) {
-    XMPI_RNM(1) XMPI_RNM(2) XMPI_RNM(3) XMPI_RNM(4) XMPI_RNM(5) XMPI_RNM(6) XMPI_RNM(7) XMPI_RNM(8)
-    default:
-      XMPI_LAUNCH((reduce_n_multi_kernel<T, OP, 0, 0>), dim3(grid), dim3(kBlock), s, es, ee, q, nsrc, ndst, npack,
-                  count);
-      break;
-  }
-#undef XMPI_RNM
-  return hipGetLastError();
+  });
 }
-
-template <typename T>
-hipError_t reduce_n_multi_op(const MultiPtrs& q, int nsrc, int ndst, size_t count, bool vec, int op, hipStream_t s,
-                             hipEvent_t es, hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: return reduce_n_multi_typed<T, OP_SUM>(q, nsrc, ndst, count, vec, s, es, ee);
-    case OP_PROD: return reduce_n_multi_typed<T, OP_PROD>(q, nsrc, ndst, count, vec, s, es, ee);
-    case OP_MIN: return reduce_n_multi_typed<T, OP_MIN>(q, nsrc, ndst, count, vec, s, es, ee);
-    case OP_MAX: return reduce_n_multi_typed<T, OP_MAX>(q, nsrc, ndst, count, vec, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
-}
-}  // namespace
 
 hipError_t launch_reduce_n_multi(void* const* dsts, int ndst, const void* const* srcs, int nsrc, size_t count,
                                  int dtype, int op, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
   if (nsrc < 1 || nsrc > kMaxReduceSrcs || ndst < 0 || ndst > kMaxReduceSrcs) return hipErrorInvalidValue;
   if (count == 0 || ndst == 0) {
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+    record_events(es, ee, s);
     return hipSuccess;
   }
   MultiPtrs q;
@@ -1267,16 +1087,25 @@ hipError_t launch_reduce_n_multi(void* const* dsts, int ndst, const void* const*
     q.dst[i] = (i < ndst) ? dsts[i] : nullptr;
     vec = vec && aligned16(q.src[i]) && aligned16(q.dst[i]);
   }
-  switch (dtype) {
-    case DT_U8: return reduce_n_multi_op<uint8_t>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_I32: return reduce_n_multi_op<int32_t>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_I64: return reduce_n_multi_op<int64_t>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_F16: return reduce_n_multi_op<_Float16>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_F32: return reduce_n_multi_op<float>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_F64: return reduce_n_multi_op<double>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    case DT_BF16: return reduce_n_multi_op<bf16_t>(q, nsrc, ndst, count, vec, op, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      if (!vec) {
+        XMPI_LAUNCH((reduce_n_multi_elem_kernel<T, OP>), dim3(grid_for(count, kBlock)), dim3(kBlock), s, es, ee, q, nsrc, ndst,
+                    count);
+        return hipGetLastError();
+      }
+      const size_t npack = count / (16 / sizeof(T));
+      const int grid = grid_for(npack, kBlock);
+      const int mode = kernel_mode_for((size_t)(nsrc + ndst) * count * sizeof(T));
+      return with_nsrc_mode<1, 2, 3, 4, 5, 6, 7, 8>(nsrc, mode, [&](auto ns, auto m) {
+        XMPI_LAUNCH((reduce_n_multi_kernel<T, OP, decltype(ns)::value, decltype(m)::value>), dim3(grid), dim3(kBlock), s, es, ee, q,
+                    nsrc, ndst, npack, count);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_copy_pairs(void* const* dsts, const void* const* srcs, int n, size_t bytes, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
@@ -1288,24 +1117,16 @@ hipError_t launch_copy_pairs(void* const* dsts, const void* const* srcs, int n, 
     if (i < n && (!aligned16(q.src[i]) || !aligned16(q.dst[i]))) return hipErrorInvalidValue;
   }
   if (bytes == 0) {
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+    record_events(es, ee, s);
     return hipSuccess;
   }
   const size_t npack = bytes / 16;
-  const int grid = grid_for(npack, kBlock);                       // (as reduce_n_multi_typed: one packet per lane)
+  const int grid = grid_for(npack, kBlock);                       // (as launch_reduce_n_multi: one packet per lane)
   const int mode = kernel_mode_for((size_t)(2 * n) * bytes);      // ... and its cache policy for that many bytes
-#define XMPI_CPP(NS)                                                                                                  \
-  case NS:                                                                                                            \
-    if (mode != 0) XMPI_LAUNCH((copy_pairs_kernel<NS, 2>), dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);  \
-    else XMPI_LAUNCH((copy_pairs_kernel<NS, 0>), dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);            \
-    break;
-  switch (n) {
-    XMPI_CPP(1) XMPI_CPP(2) XMPI_CPP(3) XMPI_CPP(4) XMPI_CPP(5) XMPI_CPP(6) XMPI_CPP(7) XMPI_CPP(8)
-    default: XMPI_LAUNCH((copy_pairs_kernel<0, 0>), dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes); break;
-  }
-#undef XMPI_CPP
-  return hipGetLastError();
+  return with_nsrc_mode<1, 2, 3, 4, 5, 6, 7, 8>(n, mode, [&](auto ns, auto m) {
+    XMPI_LAUNCH((copy_pairs_kernel<decltype(ns)::value, decltype(m)::value>), dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_copy_multi(void* const* dsts, int ndst, const void* src, size_t bytes, hipStream_t s,
@@ -1322,8 +1143,7 @@ hipError_t launch_copy_multi(void* const* dsts, int ndst, const void* src, size_
       vec = vec && aligned16(dsts[i]);
     }
   if (bytes == 0 || n == 0) {
-    if (es) (void)hipEventRecord(es, s);
-    if (ee) (void)hipEventRecord(ee, s);
+    record_events(es, ee, s);
     return hipSuccess;
   }
   if (!vec) {
@@ -1332,10 +1152,10 @@ hipError_t launch_copy_multi(void* const* dsts, int ndst, const void* src, size_
   }
   const size_t npack = bytes / 16;
   const int grid = grid_for(npack + 1, (size_t)kBlock * kUnroll);
-  const int mode = kernel_mode_for((size_t)(1 + n) * bytes);
-  if (mode != 0) XMPI_LAUNCH(copy_multi_kernel<2>, dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);
-  else XMPI_LAUNCH(copy_multi_kernel<0>, dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);
-  return hipGetLastError();
+  return with_mode02(kernel_mode_for((size_t)(1 + n) * bytes), [&](auto m) {
+    XMPI_LAUNCH((copy_multi_kernel<decltype(m)::value>), dim3(grid), dim3(kBlock), s, es, ee, q, n, npack, bytes);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_count_mismatch(const void* a, const void* b, size_t bytes, uint64_t* d_out,
@@ -1363,27 +1183,14 @@ hipError_t launch_diff_stats(const void* a, const void* b, size_t count, int dty
   unsigned long long* o_nan = (unsigned long long*)d_out + 2;
   unsigned long long* o_rel = (unsigned long long*)d_out + 3;
   const dim3 grid(grid_for(count, kBlock * 8)), block(kBlock);
-  switch (dtype) {
-    case DT_F16:
-      hipLaunchKernelGGL(diff_stats_kernel<_Float16>, grid, block, 0, s, (const _Float16*)a,
-                         (const _Float16*)b, count, o_max, o_sum, o_nan, o_rel);
-      break;
-    case DT_BF16:
-      hipLaunchKernelGGL(diff_stats_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)a,
-                         (const bf16_t*)b, count, o_max, o_sum, o_nan, o_rel);
-      break;
-    case DT_F32:
-      hipLaunchKernelGGL(diff_stats_kernel<float>, grid, block, 0, s, (const float*)a, (const float*)b,
-                         count, o_max, o_sum, o_nan, o_rel);
-      break;
-    case DT_F64:
-      hipLaunchKernelGGL(diff_stats_kernel<double>, grid, block, 0, s, (const double*)a,
-                         (const double*)b, count, o_max, o_sum, o_nan, o_rel);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (std::is_integral_v<T>) return hipErrorInvalidValue;  // floats only
+    else {
+      hipLaunchKernelGGL(diff_stats_kernel<T>, grid, block, 0, s, (const T*)a, (const T*)b, count, o_max, o_sum, o_nan, o_rel);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t launch_fill(void* buf, size_t count, int dtype, int pattern, uint64_t seed, hipStream_t s) {
@@ -1409,50 +1216,33 @@ hipError_t launch_signal(uint64_t* flag, uint64_t value, hipStream_t s) {
   return hipGetLastError();
 }
 
-namespace {
-template <typename T, int OP, int NSRC, int U>
-hipError_t dsync_go(const DsyncArgs& a, int grid_x, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  const dim3 grid(grid_x < 1 ? 1 : grid_x, a.nseg < 1 ? 1 : a.nseg);
-  XMPI_LAUNCH((dsync_fold_kernel<T, OP, NSRC, U>), grid, dim3(kBlock), s, es, ee, a);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t dsync_typed(const DsyncArgs& a, int nsrc, int op, int grid_x, int unroll, hipStream_t s, hipEvent_t es,
-                       hipEvent_t ee) {
-  if (op == OP_SUM) {  // the hot operator: sources unrolled, one or two packets per lane per source in flight
-#define XMPI_DS(NS)                                                              \
-  case NS:                                                                       \
-    return unroll >= 2 ? dsync_go<T, OP_SUM, NS, 2>(a, grid_x, s, es, ee) : dsync_go<T, OP_SUM, NS, 1>(a, grid_x, s, es, ee);
-    switch (nsrc) {
-      XMPI_DS(1) XMPI_DS(2) XMPI_DS(3) XMPI_DS(4) XMPI_DS(5) XMPI_DS(6) XMPI_DS(7) XMPI_DS(8)
-      default: return dsync_go<T, OP_SUM, 0, 1>(a, grid_x, s, es, ee);
-    }
-#undef XMPI_DS
-  }
-  switch (op) {
-    case OP_PROD: return dsync_go<T, OP_PROD, 0, 1>(a, grid_x, s, es, ee);
-    case OP_MIN: return dsync_go<T, OP_MIN, 0, 1>(a, grid_x, s, es, ee);
-    case OP_MAX: return dsync_go<T, OP_MAX, 0, 1>(a, grid_x, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
-}
-}  // namespace
-
 hipError_t launch_dsync_fold(const DsyncArgs& a, int nsrc, int dtype, int op, int grid_x, int unroll, hipStream_t s,
                              hipEvent_t es, hipEvent_t ee) {
   if (a.n < 1 || a.n > kDsyncRanks || a.nseg < 0 || a.nseg > kDsyncRanks || nsrc < 0 || nsrc > kDsyncRanks)
     return hipErrorInvalidValue;
-  switch (dtype) {
-    case DT_U8: return dsync_typed<uint8_t>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_I32: return dsync_typed<int32_t>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_I64: return dsync_typed<int64_t>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_F16: return dsync_typed<_Float16>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_F32: return dsync_typed<float>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_F64: return dsync_typed<double>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    case DT_BF16: return dsync_typed<bf16_t>(a, nsrc, op, grid_x, unroll, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  const dim3 grid(grid_x < 1 ? 1 : grid_x, a.nseg < 1 ? 1 : a.nseg);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      if constexpr (OP == OP_SUM) {  // the hot operator: sources unrolled, one or two packets per lane per source in flight
+        return with_int<1, 2, 3, 4, 5, 6, 7, 8>(nsrc, [&](auto ns) {
+          constexpr int NS = decltype(ns)::value;
+          if constexpr (NS != 0) {
+            if (unroll >= 2) {
+              XMPI_LAUNCH((dsync_fold_kernel<T, OP_SUM, NS, 2>), grid, dim3(kBlock), s, es, ee, a);
+              return hipGetLastError();
+            }
+          }
+          XMPI_LAUNCH((dsync_fold_kernel<T, OP_SUM, NS, 1>), grid, dim3(kBlock), s, es, ee, a);
+          return hipGetLastError();
+        });
+      } else {
+        XMPI_LAUNCH((dsync_fold_kernel<T, OP, 0, 1>), grid, dim3(kBlock), s, es, ee, a);
+        return hipGetLastError();
+      }
+    });
+  });
 }
 
 hipError_t launch_dsync_alltoallv(const DsyncVArgs& a, int elem_size, int grid_x, hipStream_t s, hipEvent_t es, hipEvent_t ee) {

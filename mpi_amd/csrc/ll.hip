@@ -16,15 +16,10 @@
 
 #include "kdev.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace xmpi {
 namespace {
-
-#define XMPI_LAUNCH(kern, grid, block, stream, es, ee, ...)                                  \
-  do {                                                                                       \
-    if ((es) || (ee)) hipExtLaunchKernelGGL(kern, grid, block, 0, stream, es, ee, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);                      \
-  } while (0)
 
 __device__ __forceinline__ char* ll_slot(DsyncPage* page, int src, uint32_t parity) {
   return reinterpret_cast<char*>(page) + kLLOff + ((size_t)src * 2 + parity) * kLLSlotBytes;
@@ -653,28 +648,6 @@ __global__ __launch_bounds__(kLLAgentBlock) void ll_agent_kernel(LLAgentArgs a) 
   }
 }
 
-template <typename T>
-hipError_t ll_op(const DsyncLLArgs& a, int op, dim3 grid, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  if (a.coll == LL_REDUCE_SCATTER) {
-    switch (op) {
-      case OP_SUM: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_SUM>), grid, dim3(kBlock), s, es, ee, a); break;
-      case OP_PROD: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_PROD>), grid, dim3(kBlock), s, es, ee, a); break;
-      case OP_MIN: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_MIN>), grid, dim3(kBlock), s, es, ee, a); break;
-      case OP_MAX: XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP_MAX>), grid, dim3(kBlock), s, es, ee, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (op) {
-    case OP_SUM: XMPI_LAUNCH((ll_reduce_kernel<T, OP_SUM>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_PROD: XMPI_LAUNCH((ll_reduce_kernel<T, OP_PROD>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_MIN: XMPI_LAUNCH((ll_reduce_kernel<T, OP_MIN>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_MAX: XMPI_LAUNCH((ll_reduce_kernel<T, OP_MAX>), grid, dim3(kBlock), s, es, ee, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_dsync_ll(const DsyncLLArgs& a, int dtype, int op, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
@@ -691,16 +664,15 @@ hipError_t launch_dsync_ll(const DsyncLLArgs& a, int dtype, int op, hipStream_t 
     return hipGetLastError();
   }
   if (a.coll != LL_ALLREDUCE && a.coll != LL_REDUCE && a.coll != LL_REDUCE_SCATTER) return hipErrorInvalidValue;
-  switch (dtype) {
-    case DT_U8: return ll_op<uint8_t>(a, op, grid, s, es, ee);
-    case DT_I32: return ll_op<int32_t>(a, op, grid, s, es, ee);
-    case DT_I64: return ll_op<int64_t>(a, op, grid, s, es, ee);
-    case DT_F16: return ll_op<_Float16>(a, op, grid, s, es, ee);
-    case DT_F32: return ll_op<float>(a, op, grid, s, es, ee);
-    case DT_F64: return ll_op<double>(a, op, grid, s, es, ee);
-    case DT_BF16: return ll_op<bf16_t>(a, op, grid, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      if (a.coll == LL_REDUCE_SCATTER) XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP>), grid, dim3(kBlock), s, es, ee, a);
+      else XMPI_LAUNCH((ll_reduce_kernel<T, OP>), grid, dim3(kBlock), s, es, ee, a);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_ll_agent(const LLAgentArgs& a, hipStream_t s) {

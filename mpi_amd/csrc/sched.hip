@@ -20,16 +20,11 @@
 
 #include "kdev.h"
 #include "kernels.h"
+#include "launch.h"
 #include "sched_steps.h"
 
 namespace xmpi {
 namespace {
-
-#define XMPI_LAUNCH(kern, grid, block, stream, es, ee, ...)                                  \
-  do {                                                                                       \
-    if ((es) || (ee)) hipExtLaunchKernelGGL(kern, grid, block, 0, stream, es, ee, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);                      \
-  } while (0)
 
 // =====================================================================================================================
 // split form: meet
@@ -691,47 +686,6 @@ __global__ __launch_bounds__(kBlock) void p2p_agent_kernel(P2PAgentArgs a) {
 // launchers
 // =====================================================================================================================
 
-template <typename T, int OP>
-hipError_t body_go(const DsyncResolved* res, dim3 grid, int nsrc_hint, int mode, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-#define XMPI_BODY(NS)                                                                                         \
-  do {                                                                                                        \
-    if (mode == 3) XMPI_LAUNCH((dsync_body_kernel<T, OP, NS, 3>), grid, dim3(kBlock), s, es, ee, res);        \
-    else if (mode != 0) XMPI_LAUNCH((dsync_body_kernel<T, OP, NS, 2>), grid, dim3(kBlock), s, es, ee, res);   \
-    else XMPI_LAUNCH((dsync_body_kernel<T, OP, NS, 0>), grid, dim3(kBlock), s, es, ee, res);                  \
-    return hipGetLastError();                                                                                 \
-  } while (0)
-  if constexpr (OP == OP_SUM) {
-    if (nsrc_hint == 2) XMPI_BODY(2);
-    if (nsrc_hint == 4) XMPI_BODY(4);
-    if (nsrc_hint == 8) XMPI_BODY(8);
-  }
-  XMPI_BODY(0);
-#undef XMPI_BODY
-}
-
-template <typename T>
-hipError_t body_op(const DsyncResolved* res, dim3 grid, int nsrc_hint, int op, int mode, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: return body_go<T, OP_SUM>(res, grid, nsrc_hint, mode, s, es, ee);
-    case OP_PROD: return body_go<T, OP_PROD>(res, grid, nsrc_hint, mode, s, es, ee);
-    case OP_MIN: return body_go<T, OP_MIN>(res, grid, nsrc_hint, mode, s, es, ee);
-    case OP_MAX: return body_go<T, OP_MAX>(res, grid, nsrc_hint, mode, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename T>
-hipError_t sched_op(const DsyncSchedArgs& a, int op, dim3 grid, hipStream_t s, hipEvent_t es, hipEvent_t ee) {
-  switch (op) {
-    case OP_SUM: XMPI_LAUNCH((dsync_sched_kernel<T, OP_SUM>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_PROD: XMPI_LAUNCH((dsync_sched_kernel<T, OP_PROD>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_MIN: XMPI_LAUNCH((dsync_sched_kernel<T, OP_MIN>), grid, dim3(kBlock), s, es, ee, a); break;
-    case OP_MAX: XMPI_LAUNCH((dsync_sched_kernel<T, OP_MAX>), grid, dim3(kBlock), s, es, ee, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_dsync_meet(const DsyncArgs& a, DsyncResolved* out, hipStream_t s) {
@@ -747,18 +701,22 @@ hipError_t launch_dsync_body(const DsyncResolved* res, int nseg, size_t max_pack
   if (gx < 1) gx = 1;
   if (gx > 0x3fffffu) gx = 0x3fffffu;
   const dim3 grid((unsigned)gx, (unsigned)nseg);
-  // launches that stream more than the caches hold use non-temporal loads and stores (kernels.hip kernel_mode_for)
-  const int mode = sys ? 3 : get_kernel_mode() >= 0 ? get_kernel_mode() : (traffic_bytes >= (size_t)(48u << 20) ? 2 : 0);
-  switch (dtype) {
-    case DT_U8: return body_op<uint8_t>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_I32: return body_op<int32_t>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_I64: return body_op<int64_t>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_F16: return body_op<_Float16>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_F32: return body_op<float>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_F64: return body_op<double>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    case DT_BF16: return body_op<bf16_t>(res, grid, nsrc_hint, op, mode, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  // past the caches altogether for system memory, else the streaming kernels' policy (a forced 1 runs as 2)
+  const int mode = sys ? 3 : kernel_mode_for(traffic_bytes) != 0 ? 2 : 0;
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return with_op(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      auto go = [&](auto ns) {
+        return with_int<2, 3>(mode, [&](auto m) {
+          XMPI_LAUNCH((dsync_body_kernel<T, OP, decltype(ns)::value, decltype(m)::value>), grid, dim3(kBlock), s, es, ee, res);
+          return hipGetLastError();
+        });
+      };
+      if constexpr (OP == OP_SUM) return with_int<2, 4, 8>(nsrc_hint, go);  // the hot operator: 2, 4 or 8 sources unrolled
+      else return go(int_tag<0>{});
+    });
+  });
 }
 
 hipError_t launch_xcc_probe(uint32_t* mask_out, int blocks, hipStream_t s) {
@@ -795,17 +753,13 @@ hipError_t launch_dsync_sched(const DsyncSchedArgs& a, int dtype, int op, int gr
       (size_t)grid_x * (size_t)a.nchan > (size_t)kStepSlots)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)grid_x, (unsigned)a.nchan);
-  if (a.sched == SCHED_RING_ALLGATHER || a.sched == SCHED_TREE_BCAST) return sched_op<uint8_t>(a, OP_SUM, grid, s, es, ee);
-  switch (dtype) {
-    case DT_U8: return sched_op<uint8_t>(a, op, grid, s, es, ee);
-    case DT_I32: return sched_op<int32_t>(a, op, grid, s, es, ee);
-    case DT_I64: return sched_op<int64_t>(a, op, grid, s, es, ee);
-    case DT_F16: return sched_op<_Float16>(a, op, grid, s, es, ee);
-    case DT_F32: return sched_op<float>(a, op, grid, s, es, ee);
-    case DT_F64: return sched_op<double>(a, op, grid, s, es, ee);
-    case DT_BF16: return sched_op<bf16_t>(a, op, grid, s, es, ee);
-    default: return hipErrorInvalidValue;
-  }
+  const bool moves_only = a.sched == SCHED_RING_ALLGATHER || a.sched == SCHED_TREE_BCAST;  // bytes, whatever the dtype: one kernel
+  return with_dtype(moves_only ? (int)DT_U8 : dtype, [&](auto t) {
+    return with_op(moves_only ? (int)OP_SUM : op, [&](auto o) {
+      XMPI_LAUNCH((dsync_sched_kernel<typename decltype(t)::type, decltype(o)::value>), grid, dim3(kBlock), s, es, ee, a);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_sys_copy(void* dst, const void* src, size_t bytes, int grid_x, hipStream_t s) {

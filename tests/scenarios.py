@@ -3812,7 +3812,59 @@ def sc_kernel_variants(comm, args):
           + ("are identical in every case" if not differ else "DIFFER: " + ", ".join(f"{k}: {v[1]} elements in {v[0]} cases" for k, v in sorted(differ.items()))))
 
 
+def sc_dispatch_matrix(comm, args):
+    """Every dtype x every operator through each device-synchronised launcher (launch_dsync_fold, launch_dsync_body,
+    launch_dsync_sched, launch_dsync_ll): one allreduce each by the one-kernel fold (SUM under both unrolls, which are kernels of
+    their own), meet / body / done, the ring kernel (pull) and the LL lines launched -- a (dtype, operator) handed to another
+    type's or operator's kernel shows as a wrong answer.  The counters confirm that each form ran.  The bars are DESIGN.md's:
+    fold, split and LL fold in rank order (bit for bit), the ring on floats is held to allreduce_case's association tolerance.
+    Inputs: a SUM's are PAT_UNIFORM (the default of every scenario here); PROD / MIN / MAX take PAT_SIGNED as sc_zero_copy,
+    sc_split and sc_ll give them -- except the ring's PROD, which takes PAT_UNIFORM as sc_sched's does: three PAT_SIGNED f16
+    factors (multiples of 2^-12) reach below f16's subnormal spacing 2^-24, where a bound relative to the result says nothing,
+    while PAT_UNIFORM f16 products are multiples of 2^-18 and only ever round in the normal range.
+    4099 elements: packets and a ragged tail; 1001 for LL: under its 32 KiB slot limit for every dtype.  With 2 ranks the fold and
+    the split body take a source-count-specialised kernel, with 3 the fold takes its unrolled NS = 3 and the body the generic one."""
+    if comm.get_param("dsync") != 1:
+        return
+    names = ("dsync_split_bytes", "dsync_unroll", "body_sys", "agent_ll")
+    keep = {k: comm.get_param(k) for k in names}
+    counters = ("dsync_launches", "dsync_split_launches", "dsync_ll_launches", "dsync_ll_agent", "dsync_sched_launches")
+    n, n_ll = args.get("count", 4099), args.get("ll_count", 1001)
+    assert n_ll * 8 <= comm.get_param("ll_max_bytes")
+    # (what, algorithm, parameters, elements, the counters' steps: launches, split, LL, by the agent, stepped)
+    forms = [("fold, unroll 1", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 0, "dsync_unroll": 1}, n, (1, 0, 0, 0, 0)),
+             ("fold, unroll 2", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 0, "dsync_unroll": 2}, n, (1, 0, 0, 0, 0)),
+             ("split", xmpi.ALGO_ZCOPY, {"dsync_split_bytes": 1, "body_sys": 0}, n, (3, 1, 0, 0, 0)),
+             ("ring", xmpi.ALGO_RING, {}, n, None),
+             ("LL", xmpi.ALGO_LL, {"agent_ll": 0}, n_ll, None)]
+    ran = 0
+    for what, algo, params, count, steps in forms:
+        for k, v in params.items():
+            comm.set_param(k, v)
+        for dtype in KV_DTYPES:
+            for op in KV_OPS:
+                if what == "fold, unroll 2" and op != xmpi.SUM:
+                    continue  # the unroll exists for SUM only: every other operator ran its one kernel a form ago
+                pattern = xmpi.PAT_UNIFORM if op == xmpi.SUM or (what == "ring" and op == xmpi.PROD) else xmpi.PAT_SIGNED
+                before = [comm.get_param(k) for k in counters]
+                allreduce_case(comm, dtype, count, algo, op=op, pattern=pattern, exact=None if what == "ring" else True)
+                step = tuple(comm.get_param(k) - b for k, b in zip(counters, before))
+                where = f"dispatch matrix, {what}, {xmpi.DTYPE_NAME[dtype]} op={op}: the counters moved by {step}"
+                if what == "ring":
+                    assert step[4] == 1 and step[1] == 0 and step[2] == 0, where
+                elif what == "LL":
+                    assert step[2] == 1 and step[3] == 0 and step[4] == 0, where
+                else:
+                    assert step == steps, where
+                ran += 1
+    for k, v in keep.items():
+        comm.set_param(k, v)
+    assert ran == 4 * 28 + 7
+    print(f"rank {comm.rank()}/{comm.size()} dispatch matrix: {ran} allreduces, 7 dtypes x 4 operators x (fold, split, ring, LL) + SUM under unroll 2")
+
+
 SCENARIOS = {
+    "dispatch_matrix": sc_dispatch_matrix,
     "guard": sc_guard,
     "corrupt": sc_corrupt,
     "mismatch": sc_mismatch,

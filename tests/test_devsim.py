@@ -175,6 +175,9 @@ SCENARIOS = [
     ("sched", 3, {"shapes": [(1, 2)], "counts": [1, 4099], "quick": 1}),
     ("sched", 8, {"shapes": [(0, 0)], "counts": [17], "quick": 1}),
     ("split", 4, {"counts": [1, 17, 4099]}),
+    # every dtype x operator through the fold, the split form, the ring kernel and the LL lines: which instantiation a launcher picks
+    ("dispatch_matrix", 2, None),
+    ("dispatch_matrix", 3, None),
     ("multistream", 4, None),
     ("p2p_stream", 4, None),
     ("soak", 3, None),

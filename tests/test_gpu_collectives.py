@@ -220,6 +220,13 @@ def test_split_form(size):
     run_ranks("split", size, timeout=600)
 
 
+@pytest.mark.parametrize("size", [2, 3])
+def test_every_dtype_and_operator_through_every_device_synchronised_launcher(size):
+    """7 dtypes x 4 operators, one small allreduce each through the one-kernel fold (SUM under both unrolls), meet / body / done,
+    the ring kernel and the LL lines, against the CPU oracle; the counters confirm each form (sc_dispatch_matrix)"""
+    run_ranks("dispatch_matrix", size, timeout=120)
+
+
 @pytest.mark.parametrize("size", [2, 3, 8])
 def test_rank_order_forms_on_hard_floats(size):
     """every rank-order form of allreduce and reduce -- AUTO, LL lines launched and by the agent, the one-kernel fold in both

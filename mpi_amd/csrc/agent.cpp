@@ -196,7 +196,7 @@ int agent_submit_ll(xmpi_comm* c, const void* send, void* recv, size_t bytes, in
     a.ll.host_epoch = c->dsync_status_dev ? (uint64_t*)(c->dsync_status_dev + 2) : nullptr;
     a.ll.abort_word = c->dsync_abort_dev;
     a.ll.status = c->dsync_status_dev;
-    a.ll.spin_limit = c->timeout_s > 0 ? (uint64_t)c->timeout_s * 100000000ull : 0;
+    a.ll.spin_limit = spin_limit_ticks(c);
     const hipError_t e = launch_ll_agent(a, s);
     if (e == hipSuccess) c->ll_agent_launches++;
     return e;

@@ -113,7 +113,7 @@ struct xmpi_comm {
   long prof_every = 1;  // profile every k-th launch (events cost stream bubbles)
   uint64_t prof_seq[xmpi::PROF_KINDS] = {0};
 
-  // device-synchronised collectives (dsync.cpp): ranks meet through flag words in HBM, the host only enqueues
+  // device-synchronised collectives (dsync.cpp and its siblings, dsync.h): ranks meet through flag words in HBM, the host only enqueues
   long dsync = 1;                // AUTO / ZCOPY may take the device-synchronised path (XMPI_DSYNC)
   bool dsync_ok = false;         // ... and this job can: every rank has a flag page, no two ranks share a (process, GPU)
   xmpi::DsyncPage* dpage = nullptr;                       // this rank's flag page (uncached HBM)
@@ -129,7 +129,7 @@ struct xmpi_comm {
   long sched_channels = 0;           // ring channels of the stepped kernels; 0 = every link direction (1 when ranks share a GPU)
   long sched_grid = 0;               // workers (blocks) of a stepped kernel; 0 = by size, bounded like dsync_grid_cap
   long tree_piece_bytes = 256 << 10; // binary-tree broadcast: pieces of this size travel down the tree pipelined
-  // stream-ordered Send / Receive (dsync.cpp p2p_*_on_stream): message numbers per ordered pair, completion words
+  // stream-ordered Send / Receive (dsync_p2p.cpp): message numbers per ordered pair, completion words
   uint64_t p2p_out_seq[xmpi::kMaxRanks] = {0};
   uint64_t p2p_op_id = 0;
   static constexpr int kP2PDoneSlots = 64;  // ... of the stream-ordered forms; as many again for the blocking Receive's pull kernels
@@ -157,7 +157,7 @@ struct xmpi_comm {
     std::vector<void*> bufs;  // stand-ins to give back
   };
   std::vector<P2PPending> p2p_pending;  // stream-ordered operations whose completion nobody has looked at yet
-  // host slices in a blocking collective (dsync.cpp): pinned memory the GPU reads / writes directly -- [0, kHostBounce) on the
+  // host slices in a blocking collective (dsync.cpp, dsync_call.cpp): pinned memory the GPU reads / writes directly -- [0, kHostBounce) on the
   // way in, [kHostBounce, 2 kHostBounce) on the way out; allocated when the first such call comes
   static constexpr size_t kHostBounce = 256u << 10;
   char* host_bounce = nullptr;
@@ -365,6 +365,8 @@ inline int use_device(const xmpi_comm* c) {
   } while (0)
 // no-progress limit of a steady-state wait: XMPI_TIMEOUT_S, or for ever
 inline double wait_limit(const xmpi_comm* c) { return c->timeout_s > 0 ? (double)c->timeout_s : 1e18; }
+// ... and of a kernel's wait for a peer, in wall_clock64 ticks at 100 MHz; 0: for ever
+inline uint64_t spin_limit_ticks(const xmpi_comm* c) { return c->timeout_s > 0 ? (uint64_t)c->timeout_s * 100000000ull : 0; }
 void drain_worker(xmpi_comm* c);  // a blocking collective issued after non-blocking ones runs after them
 void stop_worker(xmpi_comm* c);
 // words the GPU writes and the host polls: pinned, mapped, zeroed (no host pointer without the allocation)
@@ -388,26 +390,21 @@ void dsync_finalize(xmpi_comm* c);
 void dsync_start_helper(xmpi_comm* c);
 void dsync_stop_helper(xmpi_comm* c);
 void dsync_service(xmpi_comm* c);
-// dsync.cpp
+// dsync_plan.cpp
 bool dsync_usable(const xmpi_comm* c);
+bool dsync_takes(const xmpi_comm* c, int coll, int algo);
+// dsync.cpp
 // algo: AUTO / ZCOPY (one fold per rank: one kernel, or meet / body / done), ZPUSH, RING, RHD, TREE (the stepped kernels)
 int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void* recvbuf, size_t count, int dtype,
                      int op, hipStream_t stream, bool blocking, int algo = 0);
-bool dsync_takes(const xmpi_comm* c, int coll, int algo);
-// xmpi_alltoallv with ranks that meet on the device.  The five arrays are memory the device addresses (`stream` form), or -- blocking,
-// host arrays -- go through the communicator's pinned record.  Extents and the arrays' contents in elements.
-struct VArrays {
-  const uint64_t *sendcounts, *sdispls, *recvcaps, *rdispls;
-  uint64_t* recvcounts;
-};
-int dsync_alltoallv(xmpi_comm* c, const void* sendbuf, size_t send_extent, void* recvbuf, size_t recv_extent, const VArrays& v, int dtype,
-                    hipStream_t stream, bool blocking);
+// dsync_call.cpp
 void dsync_graph_launched(xmpi_comm* c, hipStream_t stream, bool before);
+int dsync_check(xmpi_comm* c);
+void dsync_prof_harvest(xmpi_comm* c);
+// dsync_p2p.cpp
 int dsync_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest, int tag, hipStream_t stream);
 int dsync_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, int tag, hipStream_t stream);
 int dsync_p2p_reap(xmpi_comm* c);
-int dsync_check(xmpi_comm* c);
-void dsync_prof_harvest(xmpi_comm* c);
 // a rank that waits keeps serving its peers
 inline void arm(Backoff& bo, xmpi_comm* c) {
   if (c->dsync_ok) {

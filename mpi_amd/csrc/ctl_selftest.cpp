@@ -160,7 +160,7 @@ int xmpi_ctl_selftest(const char* job_key, int rank, int size, int rounds) {
     }
     if (rc != XMPI_OK) break;
     // device-synchronised collectives: a rank publishes a registration (slot k % 4), every peer reads it and
-    // acknowledges, and the owner goes on only when all have (dsync.cpp `publish` / `await_acks`, dsync_conn.cpp `dsync_service`)
+    // acknowledges, and the owner goes on only when all have (dsync_call.cpp `dsync_publish` / `dsync_await_acks`, dsync_conn.cpp `dsync_service`)
     PubTable* pt = ctl->published(rank);
     const uint64_t n = pt->count.load(std::memory_order_relaxed);
     PubEntry& pe = pt->e[n % kPubRing];

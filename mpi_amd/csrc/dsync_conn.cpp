@@ -1,4 +1,4 @@
-// dsync_conn.cpp -- the connection lifecycle of the device-synchronised collectives (dsync.cpp): the flag page of this rank
+// dsync_conn.cpp -- the connection lifecycle of the device-synchronised collectives (dsync.cpp and its siblings, dsync.h): the flag page of this rank
 // (dsync_prepare), the mapping of every peer's page and the tables its kernels read (dsync_connect), the helper thread that keeps
 // serving the peers while the application computes (dsync_start_helper / dsync_stop_helper), the way back (dsync_finalize), and
 // dsync_service -- mapping what the peers have published since this rank last looked; called from every wait loop.

@@ -70,7 +70,7 @@ int xmpi_sched_dump(int sched, int form, int in_place, int size, int rank, int r
                                                         : recv[r];
     DsyncSchedArgs ar = a;
     ar.d.me = r;
-    land[r] = sched_land_bytes(ar, in_place != 0) ? fake(r, 2) : 0;  // (as dsync.cpp lends them)
+    land[r] = sched_land_bytes(ar, in_place != 0) ? fake(r, 2) : 0;  // (as dsync_call.cpp DsyncCall::own_block lends them)
   }
   auto show = [&](uint64_t base, char* buf, size_t n) {
     if (!base) {

@@ -566,7 +566,7 @@ int xmpi_tune_decide(const double* us, int n, double margin) {
 
 // Times the schedules this job's layout offers for allreduce-sum f32, allgather, bcast and reduce on the real buffers, size class by size
 // class -- after CHECKING each one's answer at that size (above) --, lets every rank see the same (max over ranks) figures and fills the
-// table AUTO consults (dsync.cpp tuned_choice).  A candidate that was wrong on ANY rank at ANY size leaves the collective's table on
+// table AUTO consults (dsync_plan.cpp dsync_route).  A candidate that was wrong on ANY rank at ANY size leaves the collective's table on
 // EVERY rank (xmpi_get_param "tune_rejected_<collective>", xmpi_degraded(), xmpi_last_error()); a wrong DEFAULT walks the ladder the
 // mapping vote walks: split -> its system-scope data kernel -> the one-kernel fold -> (no right schedule left for some size) the ranks
 // meet on the host.  Collective: every rank calls it with the same max_bytes.  With ranks that meet on the host there is nothing to choose.
@@ -667,7 +667,7 @@ int xmpi_tune(xmpi_comm* c, size_t max_bytes) {
       }
       // "the default stays on a tie" -- and the untuned library already runs meet / body / done from dsync_split_bytes on: there
       // candidate 2 is the default, so it is decided with the two swapped
-      // (what dsync_split_bytes is compared with: the bytes one rank's kernel moves -- dsync.cpp launch)
+      // (what dsync_split_bytes is compared with: the bytes one rank's kernel moves -- dsync.cpp launch_fold)
       const size_t moved = coll == COLL_ALLREDUCE ? 2 * per_rank : coll == COLL_REDUCE ? per_rank / (size_t)c->size * (size_t)(c->size + 1)
                            : coll == COLL_ALLGATHER ? per_rank * (size_t)(c->size + 1) : 0;
       const bool split_is_default = keep_split > 0 && moved >= (size_t)keep_split && worst[2] > 0;

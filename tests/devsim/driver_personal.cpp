@@ -1,6 +1,6 @@
 // tests/devsim/driver_personal.cpp -- xmpi_reduce_scatter and xmpi_alltoall with the ranks as THREADS of this process, every rank
 // on a virtual HIP device of its own (tests/devsim), driven through the C ABI of include/xmpi.h: the personalised LL kernels
-// (ll.hip ll_reduce_scatter_kernel / ll_alltoall_kernel) and the segment plans of dsync.cpp (fold, push-only, meet / body / done,
+// (ll.hip ll_reduce_scatter_kernel / ll_alltoall_kernel) and the segment plans of dsync_plan.cpp (fold, push-only, meet / body / done,
 // all-to-all's segment per destination) under -fsanitize=thread and, in a second build, -fsanitize=undefined
 // (tests/test_personal_devsim.py builds both).  tests/devsim/driver.cpp walks the four older collectives the same way.
 //

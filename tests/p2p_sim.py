@@ -1,5 +1,5 @@
 """A model of the stream-ordered Send / Receive protocol (mpi_amd/csrc/sched.hip `p2p_send_kernel` / `p2p_recv_kernel`,
-mpi_amd/csrc/dsync.cpp `dsync_send` / `dsync_recv`) that runs on the CPU: kernels are little state machines, streams run
+mpi_amd/csrc/dsync_p2p.cpp `dsync_send` / `dsync_recv`) that runs on the CPU: kernels are little state machines, streams run
 their kernels in order, a seeded random scheduler interleaves everything that can move.
 
 What the real thing keeps in the flag allocations the model keeps in dictionaries:

@@ -272,7 +272,7 @@ def test_no_kernel_touches_a_byte_past_its_buffers(devsim_lib, devices, ranks):
 def test_host_slices_run_the_schedules_registered_buffers_run(devsim_lib, layout):
     """what a caller of the reference passes -- host slices -- is stood in for by arena blocks and takes the zero-copy path in every
     layout: rank threads of one process and processes that meet through the control block (api.cpp collective: no fallback to the
-    staged schedule, `zc_fallbacks_unregistered` stays), processes that meet on the device (dsync.cpp: `dsync_bounced`); out of place,
+    staged schedule, `zc_fallbacks_unregistered` stays), processes that meet on the device (dsync_call.cpp: `dsync_bounced`); out of place,
     in place, host operand with the result in HBM: bit-exact against the oracle (tests/scenarios.py sc_zero_copy)"""
     if layout == "threads":
         run_threads("zero_copy", 4, {"counts": [1, 4099]})

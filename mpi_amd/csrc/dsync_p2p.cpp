@@ -144,6 +144,7 @@ int dsync_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, in
   // a few blocks for a large message; every block but the first only waits for the first (a local word)
   long gx = (long)((cap_bytes + 16383) >> 14);
   gx = std::max<long>(1, std::min<long>(gx, c->dsync_sharers > 1 ? 16 : 128));
+  if (c->p2p_grid_cap > 0) gx = std::min<long>(gx, c->p2p_grid_cap);  // ("p2p_grid_cap" / XMPI_P2P_GRID_CAP, as the blocking Receive's pull kernel)
   XMPI_HIP(launch_p2p_recv(a, (int)gx, stream));
   c->p2p_pending.push_back({ds, a.done_value, {}});
   return XMPI_OK;

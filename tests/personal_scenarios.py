@@ -20,7 +20,9 @@ OPS = (xmpi.SUM, xmpi.PROD, xmpi.MIN, xmpi.MAX)
 COUNTS = (1, 3, 17, 1000, 4099, 65536 + 5)  # per block: one element, ragged lines, below / above the LL limit, unaligned blocks
 RS_ALGOS = (xmpi.ALGO_AUTO, xmpi.ALGO_ZCOPY, xmpi.ALGO_ZPUSH, xmpi.ALGO_LL, xmpi.ALGO_DIRECT)
 A2A_ALGOS = (xmpi.ALGO_AUTO, xmpi.ALGO_ZCOPY, xmpi.ALGO_LL, xmpi.ALGO_DIRECT)
-GUARD = 64  # bytes behind a receive buffer that must stay as they were
+GUARD = 64  # bytes behind a host receive slice that must stay as they were
+PAD = 256   # bytes in front of and behind a device buffer that must stay as they were (a block's alignment: the buffer keeps it)
+SEND_PAD, RECV_PAD = 0x5E, 0xC7  # different: pad copied onto pad would show
 
 _inputs = {}  # (dtype, elements, seed) -> the oracle's fill: computed once, shared by the cases, never written
 
@@ -75,28 +77,34 @@ def personal_case(comm, coll, dtype, count, algo=xmpi.ALGO_AUTO, op=xmpi.SUM, se
         assert np.all(recv[rb:] == 0xA5), f"{what}: wrote past the receive buffer"
         assert send.tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
         return
+    # both buffers inside frames: PAD bytes in front and behind, the send frame's and the receive frame's of different bytes
     if mem == "foreign":
         hip = _hip_runtime()
         s, r = ctypes.c_void_p(0), ctypes.c_void_p(0)
         comm.sync()
-        assert hip.hipMalloc(ctypes.byref(s), ctypes.c_size_t(sb)) == 0 and hip.hipMalloc(ctypes.byref(r), ctypes.c_size_t(rb + GUARD)) == 0
-        sp, rp = s.value, r.value
+        assert hip.hipMalloc(ctypes.byref(s), ctypes.c_size_t(sb + 2 * PAD)) == 0 and hip.hipMalloc(ctypes.byref(r), ctypes.c_size_t(rb + 2 * PAD)) == 0
+        sf, rf = s.value, r.value
     else:
-        send, recv = comm.alloc(sb), comm.alloc(rb + GUARD)
-        sp, rp = send.ptr, recv.ptr
-    wantd = comm.alloc(rb + GUARD).upload(np.concatenate([want.view(np.uint8), np.full(GUARD, 0xA5, dtype=np.uint8)]))
-    comm.memcpy(sp, mine.ctypes.data, sb)
-    comm.memset(rp, 0xA5, rb + GUARD)
+        send, recv = comm.alloc(sb + 2 * PAD), comm.alloc(rb + 2 * PAD)
+        sf, rf = send.ptr, recv.ptr
+    sp, rp = sf + PAD, rf + PAD
+    pad = np.full(PAD, RECV_PAD, dtype=np.uint8)
+    wantd = comm.alloc(rb + 2 * PAD).upload(np.concatenate([pad, want.view(np.uint8), pad]))
+    simage = np.concatenate([np.full(PAD, SEND_PAD, dtype=np.uint8), mine.view(np.uint8), np.full(PAD, SEND_PAD, dtype=np.uint8)])
+    comm.memcpy(sf, simage.ctypes.data, sb + 2 * PAD)
+    comm.memset(rf, RECV_PAD, rb + 2 * PAD)
+    comm.memset(rp, 0xA5, rb)
     _call(comm, coll, sp, rp, count, dtype, op, algo, stream)
-    bad = comm.count_mismatch(rp, wantd, rb + GUARD)  # (the whole buffer and the bytes behind it, on the device)
+    bad = comm.count_mismatch(rf, wantd, rb + 2 * PAD)  # (the whole buffer and the bytes in front of and behind it, on the device)
     if bad:
-        got = np.empty(rb, dtype=np.uint8)
-        comm.memcpy(got.ctypes.data, rp, rb)
-        idx = np.nonzero(got != want.view(np.uint8))[0]
-        raise AssertionError(f"{what}: {bad} bytes differ, first at byte {idx[0] if idx.size else rb} of {rb}")
-    back = np.empty(sb, dtype=np.uint8)
-    comm.memcpy(back.ctypes.data, sp, sb)
-    assert back.tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
+        got = np.empty(rb + 2 * PAD, dtype=np.uint8)
+        comm.memcpy(got.ctypes.data, rf, rb + 2 * PAD)
+        idx = np.nonzero(got != np.concatenate([pad, want.view(np.uint8), pad]))[0]
+        raise AssertionError(f"{what}: {bad} bytes differ, first at byte {int(idx[0]) - PAD} of {rb} (negative: in front of the receive buffer)")
+    back = np.empty(sb + 2 * PAD, dtype=np.uint8)
+    comm.memcpy(back.ctypes.data, sf, sb + 2 * PAD)
+    assert back[PAD:PAD + sb].tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
+    assert back.tobytes() == simage.tobytes(), f"{what}: bytes in front of or behind the send buffer were written"
     wantd.free()
     if mem == "foreign":
         comm.barrier()
@@ -273,16 +281,23 @@ def hard_personal_case(comm, coll, dtype, count, algo, op=xmpi.SUM, seed=8000):
     mine = np.concatenate([blocks[q][me] for q in range(size)])
     what = f"{coll} of hard inputs {xmpi.DTYPE_NAME[dtype]} count={count} algo={algo} op={op} rank {me}/{size}"
     rb = (count if coll == RS else size * count) * es
-    send, recv = comm.alloc(size * count * es).upload(mine), comm.alloc(rb + GUARD)
-    comm.memset(recv, 0xA5, rb + GUARD)
-    _call(comm, coll, send, recv, count, dtype, op, algo, None)
-    got = recv.download(npdt, rb // es)
+    sb = size * count * es
+    send, recv = comm.alloc(sb + 2 * PAD), comm.alloc(rb + 2 * PAD)
+    comm.memset(send, SEND_PAD, sb + 2 * PAD)
+    send.upload(mine, PAD)
+    comm.memset(recv, RECV_PAD, rb + 2 * PAD)
+    comm.memset(recv.at(PAD), 0xA5, rb)
+    _call(comm, coll, send.at(PAD), recv.at(PAD), count, dtype, op, algo, None)
+    got = recv.download(npdt, rb // es, byte_offset=PAD)
     if coll == RS:
         hi.same_floats(got, oracle.reduce_ranks(blocks[me], dtype, op), dtype, op, what)
     else:
         assert got.tobytes() == b"".join(blocks[me][r].tobytes() for r in range(size)), f"{what}: bits changed on the way"
-    assert np.all(recv.download(np.uint8, GUARD, byte_offset=rb) == 0xA5), f"{what}: wrote past the receive buffer"
-    assert send.download(npdt, size * count).tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
+    assert np.all(recv.download(np.uint8, PAD, byte_offset=PAD + rb) == RECV_PAD), f"{what}: wrote past the receive buffer"
+    assert np.all(recv.download(np.uint8, PAD) == RECV_PAD), f"{what}: wrote in front of the receive buffer"
+    assert send.download(npdt, size * count, byte_offset=PAD).tobytes() == mine.tobytes(), f"{what}: the send buffer was modified"
+    assert np.all(send.download(np.uint8, PAD) == SEND_PAD) and np.all(send.download(np.uint8, PAD, byte_offset=PAD + sb) == SEND_PAD), \
+        f"{what}: bytes in front of or behind the send buffer were written"
     send.free()
     recv.free()
 

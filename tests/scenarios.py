@@ -3863,7 +3863,337 @@ def sc_dispatch_matrix(comm, args):
     print(f"rank {comm.rank()}/{comm.size()} dispatch matrix: {ran} allreduces, 7 dtypes x 4 operators x (fold, split, ring, LL) + SUM under unroll 2")
 
 
+# ---- Send / Receive at every alignment and at the lengths where a path changes, inside canary frames -----------------------------------
+EDGE_PAD = 64  # bytes in front of and behind a payload that must stay what they were (a multiple of 16: the frame's base is 256-byte aligned)
+EDGE_SEND_PAD, EDGE_RECV_PAD = 0x11, 0xEE  # different: an over-long copy that moved pad onto an equal pad would show nothing
+EDGE_TILE = 16384             # one copy_span tile: kBlock * 4 packets of 16 bytes (mpi_amd/csrc/kdev.h)
+EDGE_ALONE = 64 << 10         # P2PAgentArgs::alone_bytes: above it every block of the agent copies (mpi_amd/csrc/agent.cpp agent_submit)
+EDGE_AGENT_MAX = 512 << 10    # the longest message the receive agent takes; the pull kernel has the rest (mpi_amd/csrc/agent.cpp agent_submit)
+EDGE_BOUNCE = 256 << 10       # kP2PBounceBytes: device -> host slice through the agent and pinned memory up to here (mpi_amd/csrc/p2p.cpp)
+EDGE_LANE_SLOTS = 4           # kHostLaneSlots: pieces of a host lane's ring (mpi_amd/csrc/ctl.h)
+EDGE_LENGTHS = [1, 15, 16, 17, EDGE_TILE - 1, EDGE_TILE, EDGE_TILE + 1, EDGE_ALONE - 1, EDGE_ALONE, EDGE_ALONE + 1,
+                EDGE_AGENT_MAX - 1, EDGE_AGENT_MAX, EDGE_AGENT_MAX + 1, (1 << 20) + 5]
+EDGE_RESIDUES = [(0, 0), (3, 3), (1, 6), (0, 5), (8, 0)]  # (source, destination) modulo 16: packets; congruent but odd; not congruent; one side odd
+EDGE_HOST_RESIDUES = [0, 3, 8, 13]  # the device side of a host leg
+EDGE_CAPACITY = 4 << 20       # the stream form's second receive of a short message: the grid follows the capacity
+EDGE_CONCURRENT = [EDGE_ALONE + 1, 70001, EDGE_AGENT_MAX + 1]
+EDGE_COUNTERS = ("p2p_direct_count", "p2p_staged_count", "p2p_lane_count", "p2p_agent_served", "p2p_agent_launches")
+_edge_master = []  # the payloads' bytes: drawn once, shared by ranks and cases, never written
+
+
+def edge_payload(n, k):
+    """message k's n bytes: a window of one fixed random array that moves with k, so that what the message before left behind
+    is not what this one expects"""
+    if not _edge_master:
+        m = np.random.default_rng(20240611).integers(0, 256, max(EDGE_LENGTHS) + 8192, dtype=np.uint8)
+        m.setflags(write=False)
+        _edge_master.append(m)
+    off = (k * 211) % 8192
+    return _edge_master[0][off:off + n]
+
+
+class EdgeFrame:
+    """a span of `n` bytes at residue `res` modulo 16 inside a frame of an xmpi_malloc block, EDGE_PAD bytes of `pad` in front and behind;
+    the frame's expected image lies beside it on the device, so that the whole of it is compared there (count_mismatch) and downloaded
+    only to name the first byte that differs"""
+
+    def __init__(self, comm, cap, pad):
+        self.comm, self.pad = comm, pad
+        self.cap = 2 * EDGE_PAD + 16 + cap
+        self.buf, self.want = comm.alloc(self.cap), comm.alloc(self.cap)
+
+    def lay(self, n, res):
+        """the frame for one message of n bytes: as long as the message needs, not as the block is.  Returns the span's address"""
+        self.n, self.off = n, EDGE_PAD + res
+        self.flen = self.off + n + EDGE_PAD
+        self.image = np.full(self.flen, self.pad, dtype=np.uint8)
+        return self.buf.at(self.off)
+
+    def expect(self, payload, filled):
+        """the image expects `payload` in the span; the frame holds it already (a source) or pad (a destination)"""
+        self.image[self.off:self.off + self.n] = payload
+        self.want.upload(self.image)
+        if filled:
+            self.comm.memcpy(self.buf.ptr, self.want.ptr, self.flen)
+        else:
+            self.comm.memset(self.buf, self.pad, self.flen)
+
+    def check(self, what):
+        bad = self.comm.count_mismatch(self.buf, self.want, self.flen)
+        if bad:
+            got = self.buf.download(np.uint8, self.flen)
+            idx = np.nonzero(got != self.image)[0]
+            raise AssertionError(f"p2p_edges {what}: {bad} bytes differ, first at {int(idx[0]) - self.off} relative to the "
+                                 f"{'destination' if self.pad == EDGE_RECV_PAD else 'source'} of {self.n} bytes "
+                                 f"(got 0x{int(got[idx[0]]):02x}, expected 0x{int(self.image[idx[0]]):02x})")
+
+    def free(self):
+        self.buf.free()
+        self.want.free()
+
+
+def _edge_counters(comm):
+    return {k: comm.get_param(k) for k in EDGE_COUNTERS}
+
+
+def _edge_confirm(comm, form, before, want):
+    """the receiver's counters say that the intended transport ran: `want` = exact deltas of direct / staged / lane / served"""
+    after = _edge_counters(comm)
+    d = {k: after[k] - before[k] for k in EDGE_COUNTERS}
+    got = {k: d[k] for k in want}
+    assert got == want, f"p2p_edges {form}: another transport ran: counters moved by {d}, expected {want}"
+    served = d["p2p_agent_served"]
+    # (how often the agent had to be launched again depends on how long the host took between two messages)
+    assert (1 <= d["p2p_agent_launches"] <= served) if served else d["p2p_agent_launches"] == 0, f"p2p_edges {form}: agent launches {d}"
+
+
+def _edge_set(comm, params):
+    """set_param on this rank (every rank calls it); returns what restores the values"""
+    keep = {k: comm.get_param(k) for k in params}
+    for k, v in params.items():
+        comm.set_param(k, v)
+    return keep
+
+
+def _edge_pairs(comm, form, params, src, dst, tags, stream=None):
+    """every length x residue pair, rank 0 -> rank 1, under `params`; returns the number of messages"""
+    rank = comm.rank()
+    keep = _edge_set(comm, params)
+    comm.barrier()
+    n_msgs = 0
+    for n in EDGE_LENGTHS:
+        for rs, rd in EDGE_RESIDUES:
+            k = next(tags)
+            what = f"form={form} n={n} res=({rs},{rd})"
+            payload = edge_payload(n, k)
+            fr = src if rank == 0 else dst
+            p = fr.lay(n, rs if rank == 0 else rd)
+            fr.expect(payload, filled=rank == 0)
+            try:
+                if rank == 0:
+                    if stream is None:
+                        comm.send(p, n, xmpi.U8, 1, k)
+                    else:
+                        comm.send_on_stream(p, n, xmpi.U8, 1, k, stream)
+                        comm.stream_sync(stream)
+                else:
+                    if stream is None:
+                        assert comm.recv(p, n, xmpi.U8, 0, k) == n, what
+                    else:
+                        comm.recv_on_stream(p, n, xmpi.U8, 0, k, stream)
+                        comm.stream_sync(stream)
+            except xmpi.XmpiError as e:  # (a peer that died in this cell is gone without a word: the survivor names the cell)
+                raise AssertionError(f"p2p_edges {what}: {e}") from e
+            fr.check(what)
+            n_msgs += 1
+    comm.barrier()
+    _edge_set(comm, keep)
+    return n_msgs
+
+
+def _edge_forms(comm, stream_form):
+    """(name, parameters, the receiver's counter deltas for the whole table) for every form of this layout"""
+    cells = [n for n in EDGE_LENGTHS for _ in EDGE_RESIDUES]
+    thr = comm.get_param("p2p_direct_bytes")  # a registered source at least this long is offered and pulled; < 0: never
+    assert thr >= 0, "p2p_edges sets the slots form itself"
+    direct = sum(1 for n in cells if n >= max(1, thr))
+    agent_on = comm.get_param("p2p_agent_us") > 0 and comm.get_param("p2p_kernel_ack") == 1
+    by_agent = sum(1 for n in cells if max(1, thr) <= n <= EDGE_AGENT_MAX) if agent_on else 0
+    pulled = lambda served: {"p2p_direct_count": direct, "p2p_staged_count": len(cells) - direct, "p2p_lane_count": 0, "p2p_agent_served": served}
+    forms = [("default", {}, pulled(by_agent))]
+    forms += [(f"pull cap={cap}", {"p2p_agent_us": 0, "p2p_grid_cap": cap}, pulled(0)) for cap in (0, 1, 3)]
+    forms += [("copy", {"p2p_kernel_ack": 0}, pulled(0))]
+    forms += [(f"slots engine={e}", {"p2p_direct_bytes": -1, "copy_engine": e},
+               {"p2p_direct_count": 0, "p2p_staged_count": len(cells), "p2p_lane_count": 0, "p2p_agent_served": 0}) for e in (0, 1)]
+    if stream_form:
+        forms += [(f"stream cap={cap}", {"p2p_grid_cap": cap, "stream": 1},
+                   {"p2p_direct_count": 0, "p2p_staged_count": 0, "p2p_lane_count": 0, "p2p_agent_served": 0}) for cap in (0, 1, 3)]
+    return forms
+
+
+def _edge_host_legs(comm, src, dst, tags):
+    """host -> device and device -> host, the device side at EDGE_HOST_RESIDUES, the host slice at an odd offset inside a padded array:
+    one lane piece, the ring exactly full, the ring wrapping, the pinned bounce"""
+    rank = comm.rank()
+    lane = comm.get_param("host_lane_bytes")
+    piece = lane // EDGE_LANE_SLOTS if lane > 0 else 65536
+    lengths = [1, 17, piece - 1, piece, piece + 1, 4 * piece, 4 * piece + 1, 9 * piece + 5, EDGE_BOUNCE - 1, EDGE_BOUNCE, EDGE_BOUNCE + 1,
+               EDGE_AGENT_MAX + 1]
+    assert max(lengths) <= max(EDGE_LENGTHS), lengths
+    cells = [(n, res) for n in lengths for res in EDGE_HOST_RESIDUES]
+    thr = comm.get_param("p2p_direct_bytes")
+    agent_on = comm.get_param("p2p_agent_us") > 0 and comm.get_param("p2p_kernel_ack") == 1
+    for leg in ("host->device", "device->host"):
+        comm.barrier()
+        before = _edge_counters(comm)
+        for n, res in cells:
+            k = next(tags)
+            what = f"form={leg} n={n} res={res}"
+            payload = edge_payload(n, k)
+            hoff = EDGE_PAD + (k * 5) % 16  # (host spans need no alignment)
+            host = np.full(hoff + n + EDGE_PAD, EDGE_SEND_PAD if rank == 0 else EDGE_RECV_PAD, dtype=np.uint8)
+            himage = host.copy()
+            himage[hoff:hoff + n] = payload
+            host_side = (leg == "host->device") == (rank == 0)
+            if host_side:
+                if rank == 0:
+                    host[hoff:hoff + n] = payload
+                    comm.send(host[hoff:hoff + n], n, xmpi.U8, 1, k)
+                else:
+                    assert comm.recv(host[hoff:hoff + n], n, xmpi.U8, 0, k) == n, what
+                bad = np.nonzero(host != himage)[0]
+                assert bad.size == 0, f"p2p_edges {what}: {bad.size} bytes of the host array differ, first at {int(bad[0]) - hoff} relative to the slice"
+            else:
+                fr = src if rank == 0 else dst
+                p = fr.lay(n, res)
+                fr.expect(payload, filled=rank == 0)
+                if rank == 0:
+                    comm.send(p, n, xmpi.U8, 1, k)
+                else:
+                    assert comm.recv(p, n, xmpi.U8, 0, k) == n, what
+                fr.check(what)
+        comm.barrier()
+        if rank == 1:
+            ns = [n for n, _ in cells]
+            if leg == "host->device":
+                if lane > 0:
+                    # a message that fits the ring (<= 4 pieces) lies there whole: the agent pulls it out of the pinned lane (it takes
+                    # EDGE_AGENT_MAX at the most); longer ones stream through the ring, pulled by p2p_pull_kernel run by run
+                    served = sum(1 for n in ns if n <= EDGE_LANE_SLOTS * piece and n <= EDGE_AGENT_MAX) if agent_on else 0
+                    want = {"p2p_direct_count": 0, "p2p_staged_count": 0, "p2p_lane_count": len(ns), "p2p_agent_served": served}
+                else:  # lanes off: bounced through the sender's HBM into the mail slots
+                    want = {"p2p_direct_count": 0, "p2p_staged_count": len(ns), "p2p_lane_count": 0, "p2p_agent_served": 0}
+            else:
+                # a registered source is offered and pulled whatever the destination; up to kP2PBounceBytes by the agent into pinned memory
+                direct = sum(1 for n in ns if thr >= 0 and n >= max(1, thr))
+                served = sum(1 for n in ns if thr >= 0 and max(1, thr) <= n <= EDGE_BOUNCE) if agent_on else 0
+                want = {"p2p_direct_count": direct, "p2p_staged_count": len(ns) - direct, "p2p_lane_count": 0, "p2p_agent_served": served}
+            _edge_confirm(comm, leg, before, want)
+            print(f"p2p_edges {leg}: {len(cells)} messages = {len(lengths)} lengths x {len(EDGE_HOST_RESIDUES)} residues")
+    return 2 * len(cells)
+
+
+def _edge_concurrent(comm, tags):
+    """rank 0 receives from every other rank at once, one thread each, the same tag: the agent serves one Receive, the ones that find it
+    busy (agent.cpp agent_submit: the agent_mu try-lock) launch the pull kernel beside it -- under p2p_grid_cap 0, 1 and 3"""
+    rank, size = comm.rank(), comm.size()
+    cap = max(EDGE_CONCURRENT)
+    frames = [EdgeFrame(comm, cap, EDGE_RECV_PAD) for _ in range(size - 1)] if rank == 0 else [EdgeFrame(comm, cap, EDGE_SEND_PAD)]
+    thr = comm.get_param("p2p_direct_bytes")
+    agent_on = comm.get_param("p2p_agent_us") > 0 and comm.get_param("p2p_kernel_ack") == 1 and thr >= 0
+    before = _edge_counters(comm)
+    rounds = 0
+    for grid_cap in (0, 1, 3):
+        keep = _edge_set(comm, {"p2p_grid_cap": grid_cap})
+        for n in EDGE_CONCURRENT:
+            k = next(tags)
+            comm.barrier()
+            if rank == 0:
+                errs = []
+                spans = {}
+                for r in range(1, size):
+                    spans[r] = frames[r - 1].lay(n, r % 16)
+                    frames[r - 1].expect(edge_payload(n, k + 31 * r), filled=False)
+
+                def one(r):
+                    try:
+                        assert comm.recv(spans[r], n, xmpi.U8, r, k) == n
+                    except BaseException as e:  # noqa: BLE001
+                        errs.append(f"from rank {r}: {e!r}")
+
+                ths = [threading.Thread(target=one, args=(r,)) for r in range(1, size)]
+                for t in ths:
+                    t.start()
+                for t in ths:
+                    t.join()
+                assert not errs, errs
+                for r in range(1, size):
+                    frames[r - 1].check(f"form=concurrent cap={grid_cap} n={n} res=({(2 * r + 1) % 16},{r % 16}) from rank {r}")
+            else:
+                what = f"form=concurrent cap={grid_cap} n={n} res=({(2 * rank + 1) % 16},{rank % 16}) rank {rank}'s source"
+                fr = frames[0]
+                p = fr.lay(n, (2 * rank + 1) % 16)
+                fr.expect(edge_payload(n, k + 31 * rank), filled=True)
+                comm.send(p, n, xmpi.U8, 0, k)
+                fr.check(what)
+            rounds += 1
+        comm.barrier()
+        _edge_set(comm, keep)
+    if rank == 0:
+        after = _edge_counters(comm)
+        d = {c: after[c] - before[c] for c in EDGE_COUNTERS}
+        msgs = rounds * (size - 1)
+        direct = msgs if thr >= 0 else 0
+        assert (d["p2p_direct_count"], d["p2p_staged_count"], d["p2p_lane_count"]) == (direct, msgs - direct, 0), d
+        # the first Receive of a round to reach the try-lock gets the agent, so it serves at least one of every round that it may take
+        # at all (<= EDGE_AGENT_MAX); how many of the others find it busy is a matter of timing
+        short = sum(1 for n in EDGE_CONCURRENT if n <= EDGE_AGENT_MAX) * 3
+        if agent_on:
+            assert short <= d["p2p_agent_served"] <= short * (size - 1), d
+            assert 1 <= d["p2p_agent_launches"] <= d["p2p_agent_served"], d
+        else:
+            assert d["p2p_agent_served"] == 0, d
+        print(f"p2p_edges concurrent: {msgs} messages = {rounds} rounds x {size - 1} senders, {d['p2p_agent_served']} by the agent, "
+              f"{msgs - d['p2p_agent_served']} beside it")
+    for fr in frames:
+        fr.free()
+
+
+def sc_p2p_edges(comm, args):
+    """Send / Receive byte for byte where copy_span (mpi_amd/csrc/kdev.h) and its four callers in sched.hip change paths: U8 payloads
+    at the lengths EDGE_LENGTHS and the (source, destination) residues EDGE_RESIDUES modulo 16, every cell in every form -- the receive
+    agent, the pull kernel (also capped to 1 and 3 blocks), the plain copy, the mail slots by both transports, the stream-ordered
+    kernels (also capped) -- each inside a frame whose every byte is compared on the device on both sides; then the host legs; with
+    more than two ranks, concurrent Receives instead.  The receiver's counters confirm each form.  args: "dsync" = what this layout's
+    get_param("dsync") must be (default 1): the stream form runs exactly where it is 1; "forms" = name prefixes to keep to (a test
+    that splits the table)."""
+    rank, size = comm.rank(), comm.size()
+    import itertools
+    tags = itertools.count(1)
+    dsync = comm.get_param("dsync")
+    assert dsync == args.get("dsync", 1), f"this layout expects dsync == {args.get('dsync', 1)}, the job has {dsync}"
+    if size > 2:
+        return _edge_concurrent(comm, tags)
+    cap = max(EDGE_CAPACITY, max(EDGE_LENGTHS))
+    src = EdgeFrame(comm, cap, EDGE_SEND_PAD) if rank == 0 else None
+    dst = EdgeFrame(comm, cap, EDGE_RECV_PAD) if rank == 1 else None
+    only = args.get("forms")
+    st = comm.stream_create() if dsync == 1 else None
+    for form, params, want in _edge_forms(comm, dsync == 1):
+        if only and not any(form.startswith(o) for o in only):
+            continue
+        params = dict(params)
+        stream = st if params.pop("stream", 0) else None
+        before = _edge_counters(comm)
+        n_msgs = _edge_pairs(comm, form, params, src, dst, tags, stream)
+        assert n_msgs == len(EDGE_LENGTHS) * len(EDGE_RESIDUES)
+        if stream is not None and params["p2p_grid_cap"] == 0:
+            # a short message once more into a capacity of 4 MiB: the receive kernel's grid follows the capacity, not the message
+            for n in (1, 17, EDGE_TILE + 1):
+                for rs, rd in EDGE_RESIDUES:
+                    k = next(tags)
+                    what = f"form={form} capacity={EDGE_CAPACITY} n={n} res=({rs},{rd})"
+                    fr = src if rank == 0 else dst
+                    p = fr.lay(n, rs if rank == 0 else rd)
+                    fr.expect(edge_payload(n, k), filled=rank == 0)
+                    if rank == 0:
+                        comm.send_on_stream(p, n, xmpi.U8, 1, k, st)
+                    else:
+                        comm.recv_on_stream(p, EDGE_CAPACITY, xmpi.U8, 0, k, st)
+                    comm.stream_sync(st)
+                    fr.check(what)
+        if rank == 1:
+            _edge_confirm(comm, form, before, want)
+            print(f"p2p_edges {form}: {n_msgs} messages = {len(EDGE_LENGTHS)} lengths x {len(EDGE_RESIDUES)} residue pairs")
+    if not only or "host" in only:
+        _edge_host_legs(comm, src, dst, tags)
+    if st is not None:
+        comm.stream_destroy(st)
+    (src or dst).free()
+
+
 SCENARIOS = {
+    "p2p_edges": sc_p2p_edges,
     "dispatch_matrix": sc_dispatch_matrix,
     "guard": sc_guard,
     "corrupt": sc_corrupt,

@@ -64,6 +64,9 @@ const (
 	Prod
 	Min
 	Max
+	// SumWide: F16 / BF16 accumulated in f32 in rank order and rounded once; Sum for every other type.  Schedules that pass
+	// partial sums between ranks (ring, halving, tree) refuse it.
+	SumWide
 )
 
 // DeviceBuffer is a typed span of this rank's HBM; it is what `data interface{}` carries on the

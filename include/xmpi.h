@@ -45,7 +45,29 @@ typedef enum {
   XMPI_DTYPE_ANY_INT = 0x7fffffff
 } xmpi_dtype;
 
-typedef enum { XMPI_SUM = 0, XMPI_PROD = 1, XMPI_MIN = 2, XMPI_MAX = 3, XMPI_OP_COUNT = 4, XMPI_OP_ANY_INT = 0x7fffffff } xmpi_op;
+/* XMPI_SUM .. XMPI_MAX fold in rank order and round after every rank's contribution: bit-identical to the host-side loop of a
+ * reference user (helloworld.go:53-81).
+ * XMPI_SUM_WIDE (no counterpart in the reference) is the sum of 16-bit floats as people who reduce them across GPUs expect it: the
+ * accumulator is wider than the wire format.  For XMPI_F16 and XMPI_BF16 with N >= 2 contributions, element i of the result is
+ *     narrow( ((f32(x0[i]) + f32(x1[i])) + f32(x2[i])) + ... + f32(xN-1[i]) )
+ * f32() is exact, the additions are IEEE f32 in rank order 0..N-1, and narrow() is applied ONCE: round to nearest even (bf16: NaN
+ * stays NaN, quiet; f16: the hardware conversion).  With a single contribution the element is copied unchanged, as XMPI_SUM does.
+ * For every other dtype XMPI_SUM_WIDE IS XMPI_SUM: it is normalised at the entry, so a rank passing SUM_WIDE on f32 matches a rank
+ * passing SUM; SUM against SUM_WIDE on f16 / bf16 are different calls (XMPI_ERR_ARG, "not in the same call").  With 2 ranks the two
+ * give the same bits; with 3 / 4 / 8 ranks about 20 / 30 / 47 % of dense elements differ.
+ * Where it runs: every schedule in which all N contributions to an element meet in one lane -- AUTO, ZCOPY, ZPUSH, LL, DIRECT, the
+ * stream-ordered and captured forms, xmpi_reduce_local_n / _multi.  RING, RHD, TREE and their PUSH forms NAMED BY THE CALLER answer
+ * XMPI_ERR_UNSUPPORTED on every rank, before anything is announced: their partial sums travel between ranks in the 16-bit type, so
+ * there is nothing wide to accumulate in.  AUTO whose tuned table names one of them runs the fold instead. */
+typedef enum {
+  XMPI_SUM = 0,
+  XMPI_PROD = 1,
+  XMPI_MIN = 2,
+  XMPI_MAX = 3,
+  XMPI_SUM_WIDE = 4,
+  XMPI_OP_COUNT = 5,
+  XMPI_OP_ANY_INT = 0x7fffffff
+} xmpi_op;
 
 /* collective schedules */
 /* With one process per GPU, RING (allreduce, allgather), RHD (allreduce) and TREE (bcast) are ONE kernel per rank that
@@ -396,7 +418,10 @@ int xmpi_alltoallv_on_stream(xmpi_comm* comm, const void* sendbuf, size_t send_e
 /* ---- local kernels (the HBM-bound pieces, exposed for parity tests and rooflines) --------- */
 
 /* (No counterpart in the reference: a reference user adds on the host what Receive delivered, the helloworld.go:53-81 idiom.)
- * dst[i] = a[i] op b[i]  (the per-chunk reduction every ring / halving step runs). */
+ * dst[i] = a[i] op b[i]  (the per-chunk reduction every ring / halving step runs).  XMPI_SUM_WIDE runs as XMPI_SUM here: with two
+ * operands they are the same bits -- the f32 sum of two 16-bit floats rounded once IS their correctly rounded sum, which is what
+ * XMPI_SUM computes (bf16: exactly so; f16: the packed add rounds the exact sum to nearest even as well).  (The same holds for
+ * xmpi_reduce_local_batch, the ring step's launch of several such reductions.) */
 int xmpi_reduce_local(xmpi_comm* comm, void* dst, const void* a, const void* b, size_t count,
                       xmpi_dtype dtype, xmpi_op op);
 /* dst[i] = ((src[0][i] op src[1][i]) op src[2][i]) ... strictly left to right, nsrc <= 16 -- the order in which a reference

@@ -180,7 +180,7 @@ int agent_submit_ll(xmpi_comm* c, const void* send, void* recv, size_t bytes, in
   AgentLine line = ll_line(c);
   if (c->ll_agent_running && line.gone()) c->ll_agent_running = false;  // it said it went: started again below
   const uint64_t meta = (uint64_t)(ll_coll & 3) | ((uint64_t)(root & 15) << kAgentLLRootShift) |
-                        ((uint64_t)(dtype & 7) << kAgentLLDtypeShift) | ((uint64_t)(op & 3) << kAgentLLOpShift) |
+                        ((uint64_t)(dtype & 7) << kAgentLLDtypeShift) | ((uint64_t)(op & 7) << kAgentLLOpShift) |
                         ((uint64_t)(consecutive ? 1 : 0) << kAgentLLConsecutiveShift);
   const uint64_t seq = line.post((uint64_t)(uintptr_t)send, (uint64_t)(uintptr_t)recv, meta, bytes);
   auto launch = [&](hipStream_t s) {

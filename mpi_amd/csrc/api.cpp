@@ -139,7 +139,8 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
   if (algo == XMPI_ALGO_TREE_PUSH) algo = XMPI_ALGO_TREE;
   PlanParams pp;
   pp.coll = coll;
-  pp.algo = algo;
+  // (XMPI_SUM_WIDE, reduce: staged AUTO picks the TREE for short messages -- partial sums in T; the one-hop table folds at the root)
+  pp.algo = (op == XMPI_SUM_WIDE && coll == COLL_REDUCE && algo == XMPI_ALGO_AUTO) ? (int)XMPI_ALGO_DIRECT : algo;
   pp.size = c->size;
   pp.rank = c->rank;
   pp.root = root;
@@ -217,6 +218,14 @@ static int collective(xmpi_comm* c, int coll, int algo, int root, const void* se
   if (es == 0 || op < 0 || op >= XMPI_OP_COUNT || root < 0 || root >= c->size || algo < 0 || algo >= XMPI_ALGO_COUNT) {
     set_last_error("bad dtype / op / root / algo");
     return XMPI_ERR_ARG;
+  }
+  // XMPI_SUM_WIDE: XMPI_SUM for every type but f16 / bf16; there, a stepped schedule the caller names is refused -- its partial sums
+  // travel between ranks in the 16-bit type, so no wide accumulator exists.  From the arguments alone: every rank answers alike,
+  // before anything is announced or lent.
+  op = normal_op(dtype, op);
+  if (op == XMPI_SUM_WIDE && coll_reduces(coll) && algo_stepped(algo)) {
+    set_last_error(std::string("XMPI_SUM_WIDE has no ") + algo_name(algo) + " schedule: ring, halving and tree pass partial sums between ranks in the 16-bit type (auto | zcopy | zpush | ll | direct)");
+    return XMPI_ERR_UNSUPPORTED;
   }
   // reduce-scatter and all-to-all: the schedules that exist for them, decided from the arguments alone (every rank answers alike)
   if (coll_personal(coll) && !personal_algo_ok(coll, algo)) return XMPI_ERR_UNSUPPORTED;
@@ -513,6 +522,7 @@ static int on_stream(xmpi_comm* c, int coll, int root, const void* sendbuf, void
     set_last_error("bad dtype / op / root");
     return XMPI_ERR_ARG;
   }
+  op = normal_op(dtype, op);
   if (count == 0) return XMPI_OK;
   if (!sendbuf || !recvbuf) {
     set_last_error("null buffer");
@@ -768,10 +778,13 @@ int xmpi_request_wait(xmpi_request* r) {
 int xmpi_allreduce_repeat(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, xmpi_op op,
                           int algo, int iters) {
   XMPI_ENTER(c);
+  if (op >= 0 && op < XMPI_OP_COUNT) op = (xmpi_op)normal_op((int)dtype, (int)op);
+  // (XMPI_SUM_WIDE on a stepped schedule: refused by collective() below, from the arguments alone)
+  const bool wide_stepped = op == XMPI_SUM_WIDE && algo_stepped(algo);
   // Ranks that meet on the device: the steps are ENQUEUED back to back on the communicator's stream and waited for
   // once -- what a stream-ordered caller does, and what the device rendezvous is for (no host round trip per
   // step).  Sampled launches carry their own events, read when the last step has been waited for.
-  const bool on_device = count > 0 && sendbuf && recvbuf && xmpi_dtype_size(dtype) && algo >= 0 && algo < XMPI_ALGO_COUNT &&
+  const bool on_device = count > 0 && sendbuf && recvbuf && xmpi_dtype_size(dtype) && algo >= 0 && algo < XMPI_ALGO_COUNT && !wide_stepped &&
                          dsync_takes(c, COLL_ALLREDUCE, algo) && is_device_pointer(sendbuf) && is_device_pointer(recvbuf);
   if (on_device) {
     drain_worker(c);

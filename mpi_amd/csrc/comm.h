@@ -364,6 +364,15 @@ inline int use_device(const xmpi_comm* c) {
     ::xmpi::t_api_call = (c)->api_calls.fetch_add(1, std::memory_order_relaxed) + 1; \
   } while (0)
 // no-progress limit of a steady-state wait: XMPI_TIMEOUT_S, or for ever
+// XMPI_SUM_WIDE is XMPI_SUM for every type but the two 16-bit floats (include/xmpi.h): said once, at the C entry, before a route
+// or a call signature is formed -- a rank passing SUM_WIDE on f32 is in the same call as a rank passing SUM
+inline int normal_op(int dtype, int op) { return (op == XMPI_SUM_WIDE && dtype != XMPI_F16 && dtype != XMPI_BF16) ? (int)XMPI_SUM : op; }
+// the schedules whose partial sums travel between ranks as T: no wide accumulator exists for them
+inline bool algo_stepped(int algo) {
+  return algo == XMPI_ALGO_RING || algo == XMPI_ALGO_RHD || algo == XMPI_ALGO_TREE || algo == XMPI_ALGO_RING_PUSH ||
+         algo == XMPI_ALGO_RHD_PUSH || algo == XMPI_ALGO_TREE_PUSH;
+}
+
 inline double wait_limit(const xmpi_comm* c) { return c->timeout_s > 0 ? (double)c->timeout_s : 1e18; }
 // ... and of a kernel's wait for a peer, in wall_clock64 ticks at 100 MHz; 0: for ever
 inline uint64_t spin_limit_ticks(const xmpi_comm* c) { return c->timeout_s > 0 ? (uint64_t)c->timeout_s * 100000000ull : 0; }

@@ -352,7 +352,7 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   const bool capturing = call.capturing;
 
   // route: a refused call and an LL call end here
-  const DsyncRoute rt = dsync_route(c, coll, algo, k.unit, capturing);
+  const DsyncRoute rt = dsync_route(c, coll, algo, k.unit, capturing, op == XMPI_SUM_WIDE && coll_reduces(coll));
   if (rt.refused >= 0) return dsync_refuse(coll, rt.refused);
   if (rt.form == DsyncRoute::LL) return dsync_ll(call, k, sendbuf, recvbuf);
   RoctxRange range("xmpi:dsync %s algo=%s bytes=%zu epoch=%llu %s", coll_name(coll), algo_name(rt.algo), k.send_bytes,

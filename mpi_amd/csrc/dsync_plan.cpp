@@ -59,7 +59,7 @@ bool dsync_takes(const xmpi_comm* c, int coll, int algo) {
 // From the communicator and the arguments only -- the same answer on every rank, so every rank refuses alike, hands the same calls
 // to LL and launches the same form.  Pure: no HIP, no counters, no error text.
 // unit: the message -- reduce-scatter, all-to-all: the BLOCK, which is what a slot of LL lines has to hold and what every link carries
-DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool capturing) {
+DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool capturing, bool wide) {
   DsyncRoute rt;
   rt.unroll = (int)std::max<long>(1, std::min<long>(2, c->dsync_unroll));
   // the schedule: what the caller named, or the library's own table (xmpi_tune fills it; untuned: the zero-copy fold, split by size)
@@ -70,6 +70,10 @@ DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool
       if (c->tune_algo[coll][cls] >= 0) algo = c->tune_algo[coll][cls];
       if (c->tune_split[coll][cls] >= 0) rt.split_pref = c->tune_split[coll][cls];
       if (c->tune_unroll[coll][cls] > 0) rt.unroll = c->tune_unroll[coll][cls];
+      // XMPI_SUM_WIDE (f16 / bf16): a stepped schedule passes partial sums between ranks in the 16-bit type -- where the table names
+      // one, the fold runs instead (as under capture below: by the arguments, so every rank decides alike).  A caller naming one
+      // never gets here: api.cpp refuses.
+      if (wide && algo_stepped(algo)) algo = XMPI_ALGO_ZCOPY;
     }
     // untuned: short messages go as {data, flag} lines (ll.hip) -- one one-way hop instead of two round trips
     if (algo == XMPI_ALGO_AUTO && c->zero_copy && unit <= (size_t)std::max<long>(0, c->ll_bytes)) algo = XMPI_ALGO_LL;

@@ -25,7 +25,9 @@ constexpr int kBlock = 256;      // 4 waves: one per SIMD
 constexpr int kUnroll = 4;       // 16-byte packets per lane per operand in flight
 
 enum { DT_U8 = 0, DT_I32 = 1, DT_I64 = 2, DT_F16 = 3, DT_F32 = 4, DT_F64 = 5, DT_BF16 = 6 };
-enum { OP_SUM = 0, OP_PROD = 1, OP_MIN = 2, OP_MAX = 3 };
+// OP_SUM_WIDE (XMPI_SUM_WIDE): _Float16 / bf16_t only, and only in the kernels that see all N contributions to an element in one
+// lane (FoldAcc below); the launchers hand it to nothing else (launch.h with_fold_op)
+enum { OP_SUM = 0, OP_PROD = 1, OP_MIN = 2, OP_MAX = 3, OP_SUM_WIDE = 4 };
 
 struct bf16_t {
   uint16_t bits;
@@ -39,6 +41,7 @@ typedef unsigned int pack_t __attribute__((ext_vector_type(4)));
 
 template <typename T, int OP>
 __device__ __forceinline__ T combine(T a, T b) {
+  static_assert(OP >= OP_SUM && OP <= OP_MAX, "a two-operand combine has the four operators (the last branch below is MAX)");
   if constexpr (OP == OP_SUM) return a + b;
   else if constexpr (OP == OP_PROD) return a * b;
   else if constexpr (OP == OP_MIN) return (b < a) ? b : a;
@@ -55,6 +58,7 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 
 template <int OP>
 __device__ __forceinline__ bf16_t combine_bf16(bf16_t a, bf16_t b) {
+  static_assert(OP >= OP_SUM && OP <= OP_MAX, "a two-operand combine has the four operators");
   float x = bf16_to_f32(a.bits), y = bf16_to_f32(b.bits);
   if constexpr (OP == OP_SUM) return bf16_t{f32_to_bf16(x + y)};
   else if constexpr (OP == OP_PROD) return bf16_t{f32_to_bf16(x * y)};
@@ -108,6 +112,93 @@ __device__ __forceinline__ pack_t combine16(pack_t a, pack_t b) {
     return r.u;
   }
 }
+
+// 8-byte line (ll.hip: the payload of a {data, flag} line)
+template <typename T, int OP>
+__device__ __forceinline__ uint64_t combine8(uint64_t a, uint64_t b) {
+  constexpr int N = 8 / sizeof(T);
+  union {
+    uint64_t u;
+    T e[N];
+  } x, y, r;
+  x.u = a;
+  y.u = b;
+#pragma unroll
+  for (int i = 0; i < N; i++) r.e[i] = combine_any<T, OP>(x.e[i], y.e[i]);
+  return r.u;
+}
+
+// ---- the accumulator of a fold: first source, N-1 times add(), result() ----------------------------------------------------
+// W is what a lane holds of every source: a 16-byte packet (pack_t), the 8 payload bytes of an LL line (uint64_t) or one element (T).
+// Every operator but OP_SUM_WIDE accumulates in W itself -- combine16 / combine8 / combine_any per source, one rounding each, which
+// is "bit-identical to a host sum in rank order".  OP_SUM_WIDE (_Float16, bf16_t) holds the sizeof(W) / 2 elements as floats:
+//   narrow( ((f32(x0) + f32(x1)) + f32(x2)) + ... )      f32() exact, IEEE f32 additions in source order, narrow() ONCE --
+// bf16: f32_to_bf16 above (round to nearest even, its NaN rule); f16: the conversion (_Float16)f, round to nearest even.
+// Plain C++ conversions: tests/devsim compiles this for the host.
+template <typename T>
+__device__ __forceinline__ float widen1(T v) {
+  static_assert(sizeof(T) == 2, "_Float16 or bf16_t");
+  if constexpr (__is_same(T, _Float16)) return (float)v;
+  else return bf16_to_f32(v.bits);
+}
+template <typename T>
+__device__ __forceinline__ T narrow1(float f) {
+  static_assert(sizeof(T) == 2, "_Float16 or bf16_t");
+  if constexpr (__is_same(T, _Float16)) return (_Float16)f;
+  else return bf16_t{f32_to_bf16(f)};
+}
+template <typename T, typename W>
+__device__ __forceinline__ void widen_word(W w, float (&f)[sizeof(W) / 2]) {
+  union { W u; T e[sizeof(W) / 2]; } x;
+  x.u = w;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(W) / 2); i++) f[i] = widen1<T>(x.e[i]);
+}
+template <typename T, typename W>
+__device__ __forceinline__ W narrow_word(const float (&f)[sizeof(W) / 2]) {
+  union { W u; T e[sizeof(W) / 2]; } r;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(W) / 2); i++) r.e[i] = narrow1<T>(f[i]);
+  return r.u;
+}
+// a 16-byte packet of 8 halves / bfloat16s <-> 8 floats
+template <typename T>
+__device__ __forceinline__ void widen16(pack_t p, float (&f)[8]) { widen_word<T, pack_t>(p, f); }
+template <typename T>
+__device__ __forceinline__ pack_t narrow16(const float (&f)[8]) { return narrow_word<T, pack_t>(f); }
+
+template <typename T, int OP>
+constexpr bool kWideFold = OP == OP_SUM_WIDE && (__is_same(T, _Float16) || __is_same(T, bf16_t));
+
+template <typename T, int OP, typename W, bool WIDE = kWideFold<T, OP>>
+struct FoldAcc {
+  static_assert(OP != OP_SUM_WIDE, "OP_SUM_WIDE is OP_SUM for every type but _Float16 / bf16_t: the launcher says so (with_fold_op)");
+  W v;
+  __device__ __forceinline__ explicit FoldAcc(W first) : v(first) {}
+  __device__ __forceinline__ void add(W x) {
+    if constexpr (__is_same(W, pack_t)) v = combine16<T, OP>(v, x);
+    else if constexpr (__is_same(W, T)) v = combine_any<T, OP>(v, x);
+    else v = combine8<T, OP>(v, x);
+  }
+  __device__ __forceinline__ W result() const { return v; }
+};
+template <typename T, int OP, typename W>
+struct FoldAcc<T, OP, W, true> {
+  static constexpr int N = sizeof(W) / 2;
+  float f[N];
+  __device__ __forceinline__ explicit FoldAcc(W first) { widen_word<T, W>(first, f); }
+  __device__ __forceinline__ void add(W x) {
+    float g[N];
+    widen_word<T, W>(x, g);
+#pragma unroll
+    for (int i = 0; i < N; i++) f[i] += g[i];
+  }
+  __device__ __forceinline__ W result() const { return narrow_word<T, W>(f); }
+};
+template <typename T, int OP>
+using Acc16 = FoldAcc<T, OP, pack_t>;  // a packet
+template <typename T, int OP>
+using Acc1 = FoldAcc<T, OP, T>;        // one element (ragged tails, buffers at odd alignments)
 
 // ---- cache policy of the streaming accesses ----------------------------------------------------
 // MODE 0: plain loads and stores.  MODE 1: non-temporal loads and stores.  MODE 2: non-temporal

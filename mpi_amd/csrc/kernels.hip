@@ -160,24 +160,23 @@ __global__ __launch_bounds__(kBlock) void reduce_n_kernel(T* dst, SrcPtrs srcs, 
       pack_t v[NSRC];
 #pragma unroll
       for (int s = 0; s < NSRC; s++) v[s] = ldp<MODE>(reinterpret_cast<const pack_t*>(srcs.p[s]) + i);
-      pack_t acc = v[0];
+      Acc16<T, OP> acc(v[0]);
 #pragma unroll
-      for (int s = 1; s < NSRC; s++) acc = combine16<T, OP>(acc, v[s]);
-      stp<MODE>(pd + i, acc);
+      for (int s = 1; s < NSRC; s++) acc.add(v[s]);
+      stp<MODE>(pd + i, acc.result());
     } else {
-      pack_t acc = reinterpret_cast<const pack_t*>(srcs.p[0])[i];
-      for (int s = 1; s < nsrc; s++)
-        acc = combine16<T, OP>(acc, reinterpret_cast<const pack_t*>(srcs.p[s])[i]);
-      pd[i] = acc;
+      Acc16<T, OP> acc(reinterpret_cast<const pack_t*>(srcs.p[0])[i]);
+      for (int s = 1; s < nsrc; s++) acc.add(reinterpret_cast<const pack_t*>(srcs.p[s])[i]);
+      pd[i] = acc.result();
     }
   }
   constexpr size_t N = 16 / sizeof(T);
   const size_t done = npack * N;
   if (blockIdx.x == 0 && done + threadIdx.x < count) {
     const size_t i = done + threadIdx.x;
-    T acc = reinterpret_cast<const T*>(srcs.p[0])[i];
-    for (int s = 1; s < nsrc; s++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(srcs.p[s])[i]);
-    dst[i] = acc;
+    Acc1<T, OP> acc(reinterpret_cast<const T*>(srcs.p[0])[i]);
+    for (int s = 1; s < nsrc; s++) acc.add(reinterpret_cast<const T*>(srcs.p[s])[i]);
+    dst[i] = acc.result();
   }
 }
 
@@ -207,12 +206,14 @@ __global__ __launch_bounds__(kBlock) void reduce_n_multi_kernel(MultiPtrs q, int
       pack_t v[NSRC];
 #pragma unroll
       for (int s = 0; s < NSRC; s++) v[s] = ldp<MODE>(reinterpret_cast<const pack_t*>(q.src[s]) + i);
-      acc = v[0];
+      Acc16<T, OP> w(v[0]);
 #pragma unroll
-      for (int s = 1; s < NSRC; s++) acc = combine16<T, OP>(acc, v[s]);
+      for (int s = 1; s < NSRC; s++) w.add(v[s]);
+      acc = w.result();
     } else {
-      acc = reinterpret_cast<const pack_t*>(q.src[0])[i];
-      for (int s = 1; s < nsrc; s++) acc = combine16<T, OP>(acc, reinterpret_cast<const pack_t*>(q.src[s])[i]);
+      Acc16<T, OP> w(reinterpret_cast<const pack_t*>(q.src[0])[i]);
+      for (int s = 1; s < nsrc; s++) w.add(reinterpret_cast<const pack_t*>(q.src[s])[i]);
+      acc = w.result();
     }
 #pragma unroll
     for (int k = 0; k < kMaxReduceSrcs; k++)
@@ -222,8 +223,9 @@ __global__ __launch_bounds__(kBlock) void reduce_n_multi_kernel(MultiPtrs q, int
   const size_t done = npack * N;
   if (blockIdx.x == 0 && done + threadIdx.x < count) {
     const size_t i = done + threadIdx.x;
-    T acc = reinterpret_cast<const T*>(q.src[0])[i];
-    for (int s = 1; s < nsrc; s++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(q.src[s])[i]);
+    Acc1<T, OP> w(reinterpret_cast<const T*>(q.src[0])[i]);
+    for (int s = 1; s < nsrc; s++) w.add(reinterpret_cast<const T*>(q.src[s])[i]);
+    const T acc = w.result();
     for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(q.dst[k])[i] = acc;
   }
 }
@@ -257,8 +259,9 @@ template <typename T, int OP>
 __global__ __launch_bounds__(kBlock) void reduce_n_multi_elem_kernel(MultiPtrs q, int nsrc, int ndst, size_t count) {
   const size_t stride = (size_t)gridDim.x * kBlock;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
-    T acc = reinterpret_cast<const T*>(q.src[0])[i];
-    for (int s = 1; s < nsrc; s++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(q.src[s])[i]);
+    Acc1<T, OP> w(reinterpret_cast<const T*>(q.src[0])[i]);
+    for (int s = 1; s < nsrc; s++) w.add(reinterpret_cast<const T*>(q.src[s])[i]);
+    const T acc = w.result();
     for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(q.dst[k])[i] = acc;
   }
 }
@@ -703,9 +706,10 @@ __global__ __launch_bounds__(kBlock) void dsync_fold_kernel(DsyncArgs a) {
                 v[u][k] = ldp<2>(reinterpret_cast<const pack_t*>(sp[k]) + base + (size_t)u * kBlock + t);
 #pragma unroll
             for (int u = 0; u < U; u++) {
-              pack_t acc = v[u][0];
+              Acc16<T, OP> w(v[u][0]);
 #pragma unroll
-              for (int k = 1; k < NSRC; k++) acc = combine16<T, OP>(acc, v[u][k]);
+              for (int k = 1; k < NSRC; k++) w.add(v[u][k]);
+              const pack_t acc = w.result();
 #pragma unroll
               for (int k = 0; k < kDsyncRanks; k++)
                 if (k < ndst) stp<1>(reinterpret_cast<pack_t*>(dp[k]) + base + (size_t)u * kBlock + t, acc);
@@ -714,9 +718,10 @@ __global__ __launch_bounds__(kBlock) void dsync_fold_kernel(DsyncArgs a) {
             for (int u = 0; u < U; u++) {
               const size_t i = base + (size_t)u * kBlock + t;
               if (i >= npack) break;
-              pack_t acc = ldp<2>(reinterpret_cast<const pack_t*>(sp[0]) + i);
+              Acc16<T, OP> w(ldp<2>(reinterpret_cast<const pack_t*>(sp[0]) + i));
 #pragma unroll
-              for (int k = 1; k < NSRC; k++) acc = combine16<T, OP>(acc, ldp<2>(reinterpret_cast<const pack_t*>(sp[k]) + i));
+              for (int k = 1; k < NSRC; k++) w.add(ldp<2>(reinterpret_cast<const pack_t*>(sp[k]) + i));
+              const pack_t acc = w.result();
 #pragma unroll
               for (int k = 0; k < kDsyncRanks; k++)
                 if (k < ndst) stp<1>(reinterpret_cast<pack_t*>(dp[k]) + i, acc);
@@ -725,8 +730,9 @@ __global__ __launch_bounds__(kBlock) void dsync_fold_kernel(DsyncArgs a) {
         }
       } else {
         for (size_t i = (size_t)blockIdx.x * kBlock + t; i < npack; i += (size_t)gridDim.x * kBlock) {
-          pack_t acc = ldp<2>(reinterpret_cast<const pack_t*>(sh.src[0]) + i);
-          for (int k = 1; k < nsrc; k++) acc = combine16<T, OP>(acc, ldp<2>(reinterpret_cast<const pack_t*>(sh.src[k]) + i));
+          Acc16<T, OP> w(ldp<2>(reinterpret_cast<const pack_t*>(sh.src[0]) + i));
+          for (int k = 1; k < nsrc; k++) w.add(ldp<2>(reinterpret_cast<const pack_t*>(sh.src[k]) + i));
+          const pack_t acc = w.result();
 #pragma unroll
           for (int k = 0; k < kDsyncRanks; k++)
             if (k < ndst) stp<1>(reinterpret_cast<pack_t*>(dp[k]) + i, acc);
@@ -735,14 +741,16 @@ __global__ __launch_bounds__(kBlock) void dsync_fold_kernel(DsyncArgs a) {
       const size_t done = npack * N;  // ragged tail (< 16 bytes): the first lanes of the segment's block 0
       if (blockIdx.x == 0 && done + t < count) {
         const size_t i = done + t;
-        T acc = reinterpret_cast<const T*>(sh.src[0])[i];
-        for (int k = 1; k < nsrc; k++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(sh.src[k])[i]);
+        Acc1<T, OP> w(reinterpret_cast<const T*>(sh.src[0])[i]);
+        for (int k = 1; k < nsrc; k++) w.add(reinterpret_cast<const T*>(sh.src[k])[i]);
+        const T acc = w.result();
         for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(sh.dst[k])[i] = acc;
       }
     } else {  // some buffer is not 16-byte aligned: one element per lane
       for (size_t i = (size_t)blockIdx.x * kBlock + t; i < count; i += (size_t)gridDim.x * kBlock) {
-        T acc = reinterpret_cast<const T*>(sh.src[0])[i];
-        for (int k = 1; k < nsrc; k++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(sh.src[k])[i]);
+        Acc1<T, OP> w(reinterpret_cast<const T*>(sh.src[0])[i]);
+        for (int k = 1; k < nsrc; k++) w.add(reinterpret_cast<const T*>(sh.src[k])[i]);
+        const T acc = w.result();
         for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(sh.dst[k])[i] = acc;
       }
     }
@@ -971,7 +979,7 @@ hipError_t launch_reduce_n(void* dst, const void* const* srcs, int nsrc, size_t 
   }
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_fold_op<T>(op, [&](auto o) {
       const size_t npack = count / (16 / sizeof(T));
       const int grid = grid_for(npack, kBlock);
       const int mode = kernel_mode_for((size_t)(nsrc + 1) * count * sizeof(T));
@@ -1087,9 +1095,10 @@ hipError_t launch_reduce_n_multi(void* const* dsts, int ndst, const void* const*
     q.dst[i] = (i < ndst) ? dsts[i] : nullptr;
     vec = vec && aligned16(q.src[i]) && aligned16(q.dst[i]);
   }
+  if (nsrc == 1 && op == OP_SUM_WIDE) op = OP_SUM;  // one contribution: the element is copied unchanged, as OP_SUM does
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_fold_op<T>(op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
       if (!vec) {
         XMPI_LAUNCH((reduce_n_multi_elem_kernel<T, OP>), dim3(grid_for(count, kBlock)), dim3(kBlock), s, es, ee, q, nsrc, ndst,
@@ -1223,18 +1232,18 @@ hipError_t launch_dsync_fold(const DsyncArgs& a, int nsrc, int dtype, int op, in
   const dim3 grid(grid_x < 1 ? 1 : grid_x, a.nseg < 1 ? 1 : a.nseg);
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_fold_op<T>(nsrc == 1 && op == OP_SUM_WIDE ? (int)OP_SUM : op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
-      if constexpr (OP == OP_SUM) {  // the hot operator: sources unrolled, one or two packets per lane per source in flight
+      if constexpr (OP == OP_SUM || OP == OP_SUM_WIDE) {  // the hot operators: sources unrolled, one or two packets per lane per source in flight
         return with_int<1, 2, 3, 4, 5, 6, 7, 8>(nsrc, [&](auto ns) {
           constexpr int NS = decltype(ns)::value;
           if constexpr (NS != 0) {
             if (unroll >= 2) {
-              XMPI_LAUNCH((dsync_fold_kernel<T, OP_SUM, NS, 2>), grid, dim3(kBlock), s, es, ee, a);
+              XMPI_LAUNCH((dsync_fold_kernel<T, OP, NS, 2>), grid, dim3(kBlock), s, es, ee, a);
               return hipGetLastError();
             }
           }
-          XMPI_LAUNCH((dsync_fold_kernel<T, OP_SUM, NS, 1>), grid, dim3(kBlock), s, es, ee, a);
+          XMPI_LAUNCH((dsync_fold_kernel<T, OP, NS, 1>), grid, dim3(kBlock), s, es, ee, a);
           return hipGetLastError();
         });
       } else {

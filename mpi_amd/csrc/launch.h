@@ -91,6 +91,16 @@ hipError_t with_op(int op, F&& f) {
   }
 }
 
+// The fold family's operators (kernels whose lane sees every contribution to an element: reduce_n*, dsync_fold, dsync_body, the LL
+// folds): the four of with_op and OP_SUM_WIDE -- handed through for the two 16-bit float types, OP_SUM for every other T, whose sum
+// it is.  A launcher of anything else (the stepped kernels, reduce2*) keeps to with_op and answers hipErrorInvalidValue.
+template <typename T, typename F>
+hipError_t with_fold_op(int op, F&& f) {
+  if (op != OP_SUM_WIDE) return with_op(op, f);
+  if constexpr (std::is_same_v<T, _Float16> || std::is_same_v<T, bf16_t>) return f(int_tag<OP_SUM_WIDE>{});
+  else return f(int_tag<OP_SUM>{});
+}
+
 // `v` as a constant if it is one of Vs, else the constant 0 (a kernel's runtime-count / plain instantiation)
 template <int... Vs, typename F>
 hipError_t with_int(int v, F&& f) {

@@ -74,29 +74,16 @@ __device__ __forceinline__ void store8(char* p, uint64_t v, uint32_t valid) {
   }
 }
 
-template <typename T, int OP>
-__device__ __forceinline__ uint64_t combine8(uint64_t a, uint64_t b) {
-  constexpr int N = 8 / sizeof(T);
-  union {
-    uint64_t u;
-    T e[N];
-  } x, y, r;
-  x.u = a;
-  y.u = b;
-#pragma unroll
-  for (int i = 0; i < N; i++) r.e[i] = combine_any<T, OP>(x.e[i], y.e[i]);
-  return r.u;
-}
-
 // the ranks' lines in rank order: ((x0 op x1) op x2) ... -- the host-side sum of a reference user (helloworld.go:53-81), bit for bit.
-// x(p) = rank p's line (never asked for p == me)
+// x(p) = rank p's line (never asked for p == me).  (kdev.h FoldAcc over a line: combine8 per rank, or -- OP_SUM_WIDE -- the line's
+// 4 elements as floats, narrowed once)
 template <typename T, int OP, typename X>
 __device__ __forceinline__ uint64_t fold_ranks(X x, uint64_t mine8, int me, int n) {
-  uint64_t acc = me == 0 ? mine8 : x(0);
+  FoldAcc<T, OP, uint64_t> acc(me == 0 ? mine8 : x(0));
 #pragma unroll
   for (int p = 1; p < kDsyncRanks; p++)
-    if (p < n) acc = combine8<T, OP>(acc, p == me ? mine8 : x(p));
-  return acc;
+    if (p < n) acc.add(p == me ? mine8 : x(p));
+  return acc.result();
 }
 // dtype and operation fixed at compile time (the launched kernels: one instantiation each) ...
 template <typename T, int OP>
@@ -115,6 +102,9 @@ struct LLFoldRuntime {
       case OP_SUM: return fold_ranks<T, OP_SUM>(x, mine8, me, n);
       case OP_PROD: return fold_ranks<T, OP_PROD>(x, mine8, me, n);
       case OP_MIN: return fold_ranks<T, OP_MIN>(x, mine8, me, n);
+      case OP_SUM_WIDE:  // (the host hands it over for the two 16-bit float types only: agent.cpp; anything else is its OP_SUM)
+        if constexpr (kWideFold<T, OP_SUM_WIDE>) return fold_ranks<T, OP_SUM_WIDE>(x, mine8, me, n);
+        else return fold_ranks<T, OP_SUM>(x, mine8, me, n);
       default: return fold_ranks<T, OP_MAX>(x, mine8, me, n);
     }
   }
@@ -628,7 +618,7 @@ __global__ __launch_bounds__(kLLAgentBlock) void ll_agent_kernel(LLAgentArgs a) 
     const uint32_t meta = s_meta;
     const LLCall q{reinterpret_cast<const void*>(s_send), reinterpret_cast<void*>(s_recv), s_bytes, (int32_t)(meta & 3u),
                    (int32_t)((meta >> kAgentLLRootShift) & 15u)};
-    const LLFoldRuntime fold{(int)((meta >> kAgentLLDtypeShift) & 7u), (int)((meta >> kAgentLLOpShift) & 3u)};
+    const LLFoldRuntime fold{(int)((meta >> kAgentLLDtypeShift) & 7u), (int)((meta >> kAgentLLOpShift) & 7u)};
     const uint64_t epoch = sh.epoch;
     const uint32_t parity = (uint32_t)(epoch & 1u), flag = (uint32_t)epoch ? (uint32_t)epoch : 1u;
     const bool to_all = q.coll == LL_ALLREDUCE || q.coll == LL_ALLGATHER;
@@ -666,7 +656,7 @@ hipError_t launch_dsync_ll(const DsyncLLArgs& a, int dtype, int op, hipStream_t 
   if (a.coll != LL_ALLREDUCE && a.coll != LL_REDUCE && a.coll != LL_REDUCE_SCATTER) return hipErrorInvalidValue;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_fold_op<T>(op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
       if (a.coll == LL_REDUCE_SCATTER) XMPI_LAUNCH((ll_reduce_scatter_kernel<T, OP>), grid, dim3(kBlock), s, es, ee, a);
       else XMPI_LAUNCH((ll_reduce_kernel<T, OP>), grid, dim3(kBlock), s, es, ee, a);

@@ -142,19 +142,21 @@ __global__ __launch_bounds__(kBlock) void dsync_body_kernel(const DsyncResolved*
 #pragma unroll
           for (int k = 0; k < NSRC; k++) ld_sys128_issue(v[k], reinterpret_cast<const pack_t*>(sp[k]) + i);
           sys128_wait_n<NSRC>(v);
-          acc = v[0];
+          Acc16<T, OP> w(v[0]);
 #pragma unroll
-          for (int k = 1; k < NSRC; k++) acc = combine16<T, OP>(acc, v[k]);
+          for (int k = 1; k < NSRC; k++) w.add(v[k]);
+          acc = w.result();
         } else {
           pack_t v[1];
           ld_sys128_issue(v[0], reinterpret_cast<const pack_t*>(g->src[0]) + i);
           sys128_wait_n<1>(v);
-          acc = v[0];
+          Acc16<T, OP> w(v[0]);
           for (int k = 1; k < nsrc; k++) {
             ld_sys128_issue(v[0], reinterpret_cast<const pack_t*>(g->src[k]) + i);
             sys128_wait_n<1>(v);
-            acc = combine16<T, OP>(acc, v[0]);
+            w.add(v[0]);
           }
+          acc = w.result();
         }
 #pragma unroll
         for (int k = 0; k < kDsyncRanks; k++)
@@ -165,8 +167,9 @@ __global__ __launch_bounds__(kBlock) void dsync_body_kernel(const DsyncResolved*
     const size_t lanes = vec ? (size_t)kBlock : (size_t)gridDim.x * kBlock;
     if (!vec || blockIdx.x == 0)
       for (size_t i = first + (vec ? 0 : (size_t)blockIdx.x * kBlock) + t; i < count; i += lanes) {
-        T acc = ld_sys_elem(reinterpret_cast<const T*>(g->src[0]) + i);
-        for (int k = 1; k < nsrc; k++) acc = combine_any<T, OP>(acc, ld_sys_elem(reinterpret_cast<const T*>(g->src[k]) + i));
+        Acc1<T, OP> w(ld_sys_elem(reinterpret_cast<const T*>(g->src[0]) + i));
+        for (int k = 1; k < nsrc; k++) w.add(ld_sys_elem(reinterpret_cast<const T*>(g->src[k]) + i));
+        const T acc = w.result();
         for (int k = 0; k < ndst; k++) st_sys_elem(reinterpret_cast<T*>(g->dst[k]) + i, acc);
       }
     return;
@@ -180,12 +183,14 @@ __global__ __launch_bounds__(kBlock) void dsync_body_kernel(const DsyncResolved*
         pack_t v[NSRC];
 #pragma unroll
         for (int k = 0; k < NSRC; k++) v[k] = ldp<MODE>(reinterpret_cast<const pack_t*>(sp[k]) + i);
-        acc = v[0];
+        Acc16<T, OP> w(v[0]);
 #pragma unroll
-        for (int k = 1; k < NSRC; k++) acc = combine16<T, OP>(acc, v[k]);
+        for (int k = 1; k < NSRC; k++) w.add(v[k]);
+        acc = w.result();
       } else {
-        acc = ldp<MODE>(reinterpret_cast<const pack_t*>(g->src[0]) + i);
-        for (int k = 1; k < nsrc; k++) acc = combine16<T, OP>(acc, ldp<MODE>(reinterpret_cast<const pack_t*>(g->src[k]) + i));
+        Acc16<T, OP> w(ldp<MODE>(reinterpret_cast<const pack_t*>(g->src[0]) + i));
+        for (int k = 1; k < nsrc; k++) w.add(ldp<MODE>(reinterpret_cast<const pack_t*>(g->src[k]) + i));
+        acc = w.result();
       }
 #pragma unroll
       for (int k = 0; k < kDsyncRanks; k++)
@@ -194,14 +199,16 @@ __global__ __launch_bounds__(kBlock) void dsync_body_kernel(const DsyncResolved*
     const size_t done = npack * N;  // ragged tail (< 16 bytes): the first lanes of the segment's block 0
     if (blockIdx.x == 0 && done + t < count) {
       const size_t i = done + t;
-      T acc = reinterpret_cast<const T*>(g->src[0])[i];
-      for (int k = 1; k < nsrc; k++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(g->src[k])[i]);
+      Acc1<T, OP> w(reinterpret_cast<const T*>(g->src[0])[i]);
+      for (int k = 1; k < nsrc; k++) w.add(reinterpret_cast<const T*>(g->src[k])[i]);
+      const T acc = w.result();
       for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(g->dst[k])[i] = acc;
     }
   } else {  // some buffer is not 16-byte aligned: one element per lane
     for (size_t i = (size_t)blockIdx.x * kBlock + t; i < count; i += (size_t)gridDim.x * kBlock) {
-      T acc = reinterpret_cast<const T*>(g->src[0])[i];
-      for (int k = 1; k < nsrc; k++) acc = combine_any<T, OP>(acc, reinterpret_cast<const T*>(g->src[k])[i]);
+      Acc1<T, OP> w(reinterpret_cast<const T*>(g->src[0])[i]);
+      for (int k = 1; k < nsrc; k++) w.add(reinterpret_cast<const T*>(g->src[k])[i]);
+      const T acc = w.result();
       for (int k = 0; k < ndst; k++) reinterpret_cast<T*>(g->dst[k])[i] = acc;
     }
   }
@@ -705,7 +712,7 @@ hipError_t launch_dsync_body(const DsyncResolved* res, int nseg, size_t max_pack
   const int mode = sys ? 3 : kernel_mode_for(traffic_bytes) != 0 ? 2 : 0;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_fold_op<T>(op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
       auto go = [&](auto ns) {
         return with_int<2, 3>(mode, [&](auto m) {
@@ -713,7 +720,7 @@ hipError_t launch_dsync_body(const DsyncResolved* res, int nseg, size_t max_pack
           return hipGetLastError();
         });
       };
-      if constexpr (OP == OP_SUM) return with_int<2, 4, 8>(nsrc_hint, go);  // the hot operator: 2, 4 or 8 sources unrolled
+      if constexpr (OP == OP_SUM || OP == OP_SUM_WIDE) return with_int<2, 4, 8>(nsrc_hint, go);  // the hot operators: 2, 4 or 8 sources unrolled
       else return go(int_tag<0>{});
     });
   });

@@ -443,14 +443,21 @@ size_t elem_size(xmpi_dtype dt) {
   }
 }
 
+// (the caller has checked the operator: op_known below)
 template <typename T>
 T fold1(T a, T b, xmpi_op op) {
   switch (op) {
     case XMPI_SUM: return (T)(a + b);
     case XMPI_PROD: return (T)(a * b);
     case XMPI_MIN: return (b < a) ? b : a;  // spelled like the kernels and the oracle: NaN / -0 behave alike
-    default: return (a < b) ? b : a;
+    case XMPI_MAX: return (a < b) ? b : a;
+    default: return a;  // unreachable: an unknown operator is refused before anything is exchanged
   }
+}
+// XMPI_SUM_WIDE means XMPI_SUM here: it differs for the 16-bit float types only, which have no Go type and so none on this backend
+bool op_known(xmpi_op* op) {
+  if (*op == XMPI_SUM_WIDE) *op = XMPI_SUM;
+  return *op == XMPI_SUM || *op == XMPI_PROD || *op == XMPI_MIN || *op == XMPI_MAX;
 }
 template <typename T>
 void fold_into(void* acc, const void* x, size_t n, xmpi_op op) {
@@ -521,6 +528,7 @@ Error Network::Allgather(const Data& send, Data recv) {
 
 Error Network::Reduce(const Data& send, Data recv, xmpi_op op, int root) {
   if (root < 0 || root >= size_) return Error(XMPI_ERR_ARG, "mpi reduce: bad root");
+  if (!op_known(&op)) return Error(XMPI_ERR_ARG, "mpi reduce: unknown operator");
   std::vector<std::vector<uint8_t>> all;
   if (Error e = exchange(send, &all, root)) return e;
   if (rank_ != root) return Error();
@@ -546,6 +554,7 @@ Error Network::Reduce(const Data& send, Data recv, xmpi_op op, int root) {
 
 Error Network::Allreduce(const Data& send, Data recv, xmpi_op op) {
   // every rank gathers everything and folds for itself -- what the oracle's definition says, not the cheapest schedule
+  if (!op_known(&op)) return Error(XMPI_ERR_ARG, "mpi allreduce: unknown operator");
   std::vector<std::vector<uint8_t>> all;
   if (Error e = exchange(send, &all, -1)) return e;
   const size_t es = elem_size(send.dtype), bytes = send.count * es;

@@ -65,6 +65,18 @@ int xmpi_copy_local_batch(xmpi_comm* comm, void* const* dst, void* const* dst2, 
  * back into one free block, otherwise the number of the failed check. */
 int xmpi_heap_selftest(uint64_t seed, int rounds);
 
+/* Row `index` of the library's one table of knobs and diagnostics (mpi_amd/csrc/params.cpp): what xmpi_set_param / xmpi_get_param
+ * call it (NULL: none; with XMPI_PARAM_PATTERN: a prefix), the environment variable xmpi_init reads it from (NULL: none), its fixed
+ * default and its range [lo, hi].  XMPI_ERR_ARG past the last row.  Needs no communicator: what
+ * INTEGRATION.md section 5 says is held to this by the CPU suite. */
+#define XMPI_PARAM_WRITABLE 1        /* xmpi_set_param accepts it */
+#define XMPI_PARAM_BOOLEAN 2         /* any value but 0 is 1 */
+#define XMPI_PARAM_LAYOUT_DEFAULT 4  /* no fixed default: decided where the job's layout is known (*dflt means nothing) */
+#define XMPI_PARAM_READ_ONLY 8       /* xmpi_set_param refuses it */
+#define XMPI_PARAM_PATTERN 16        /* a family of names that begin with *name */
+#define XMPI_PARAM_ENV_AUTO 32       /* the environment (only) may say -1 = decide later; below lo means the same */
+int xmpi_param_info(int index, const char** name, const char** env, long* dflt, long* lo, long* hi, int* flags);
+
 #ifdef __cplusplus
 }
 #endif

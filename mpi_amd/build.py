@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra"]
 
-LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "p2p.cpp", "agent.cpp", "api.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "dsync_plan.cpp", "dsync_call.cpp", "dsync_p2p.cpp", "dsync_conn.cpp", "vcoll.cpp", "trace.cpp"]
+LIB_SOURCES = ["kernels.hip", "sched.hip", "ll.hip", "engine.cpp", "p2p.cpp", "agent.cpp", "api.cpp", "params.cpp", "pool.cpp", "init.cpp", "tune.cpp", "local.cpp", "dump.cpp", "ctl.cpp", "ctl_selftest.cpp", "plan.cpp", "zcopy.cpp", "heap.cpp", "dsync.cpp", "dsync_plan.cpp", "dsync_call.cpp", "dsync_p2p.cpp", "dsync_conn.cpp", "vcoll.cpp", "trace.cpp"]
 LIB_HEADERS = ["kernels.h", "kdev.h", "launch.h", "sched_steps.h", "comm.h", "dsync.h", "ctl.h", "plan.h", "trace.h", os.path.join("..", "..", "include", "xmpi.h"),
                os.path.join("..", "..", "include", "xmpi_test.h")]
 

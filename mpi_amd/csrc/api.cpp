@@ -1,6 +1,5 @@
 // api.cpp -- the extern "C" entry points of include/xmpi.h.  Compiled by hipcc as host code.
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -41,10 +40,7 @@ long env_long(const char* name, long dflt) {
 static size_t choose_piece(const xmpi_comm* c, size_t bytes_per_rank_chunk) {
   if (c->piece_bytes > 0) return std::min<size_t>((size_t)c->piece_bytes, c->slot_bytes);
   // ranks sharing one in-order stream have nothing to overlap: one launch per chunk
-  bool all_coloc = c->shared_stream;
-  for (int p = 0; p < c->size && all_coloc; p++)
-    if (p != c->rank && !c->peer_coloc[p]) all_coloc = false;
-  if (all_coloc) return c->slot_bytes;
+  if (c->shared_stream && all_peers_colocated(c)) return c->slot_bytes;
   // ~4 pieces per chunk so a chunk's transfer overlaps its reduction, but never below 1 MiB (a piece
   // costs a launch and an event: ~10 us, i.e. ~0.5 MiB of link time), within [1 MiB, slot]
   size_t p = 1u << 20;
@@ -424,25 +420,19 @@ int xmpi_sync(xmpi_comm* c) {
   return XMPI_OK;
 }
 
-int xmpi_send(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) {
+// xmpi_send (waits for the receiver's confirmation) and xmpi_send_nowait (xmpi_wait collects it)
+static int send_checked(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag, bool wait_ack) {
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
   if (!es || dest < 0 || dest >= c->size || (count && !buf) || tag == kVTag) {
     set_last_error("send: bad dtype / destination / buffer (or the one tag the library keeps to itself)");
     return XMPI_ERR_ARG;
   }
-  return why_peer(c, p2p_send(c, buf, count * es, (int)dtype, dest, tag), "send");
+  return why_peer(c, p2p_send(c, buf, count * es, (int)dtype, dest, tag, wait_ack), "send");
 }
 
-int xmpi_send_nowait(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) {
-  XMPI_ENTER(c);
-  const size_t es = xmpi_dtype_size(dtype);
-  if (!es || dest < 0 || dest >= c->size || (count && !buf) || tag == kVTag) {
-    set_last_error("send: bad dtype / destination / buffer (or the one tag the library keeps to itself)");
-    return XMPI_ERR_ARG;
-  }
-  return why_peer(c, p2p_send(c, buf, count * es, (int)dtype, dest, tag, /*wait_ack=*/false), "send");
-}
+int xmpi_send(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) { return send_checked(c, buf, count, dtype, dest, tag, true); }
+int xmpi_send_nowait(xmpi_comm* c, const void* buf, size_t count, xmpi_dtype dtype, int dest, int tag) { return send_checked(c, buf, count, dtype, dest, tag, false); }
 
 int xmpi_wait(xmpi_comm* c, int dest, int tag) {
   XMPI_ENTER(c);
@@ -800,9 +790,7 @@ int xmpi_allreduce_repeat(xmpi_comm* c, const void* sendbuf, void* recvbuf, size
   // stream and one launch folds everybody's chunks, so K steps are K launches enqueued back to back between two
   // rendezvous instead of K x (rendezvous, launch, wait, rendezvous).  Anything the zero-copy path cannot take
   // (unregistered buffers) falls through to the step-by-step loop -- on every rank alike, the decision is collective.
-  bool all_coloc = c->shared_stream && c->zc_group_launch && c->size > 1 && iters > 1;
-  for (int p = 0; p < c->size && all_coloc; p++)
-    if (p != c->rank && !c->peer_coloc[p]) all_coloc = false;
+  const bool all_coloc = c->shared_stream && c->zc_group_launch && c->size > 1 && iters > 1 && all_peers_colocated(c);
   int first = 0;
   if (all_coloc && count > 0 && sendbuf && recvbuf && xmpi_dtype_size(dtype) && op >= 0 && op < XMPI_OP_COUNT &&
       (algo == XMPI_ALGO_ZCOPY || (algo == XMPI_ALGO_AUTO && c->zero_copy))) {
@@ -821,191 +809,5 @@ int xmpi_allreduce_repeat(xmpi_comm* c, const void* sendbuf, void* recvbuf, size
 }
 
 int xmpi_heap_selftest(uint64_t seed, int rounds) { return heap_selftest(seed, rounds); }
-
-// ---- tuning / introspection ----------------------------------------------------------------------
-
-int xmpi_set_param(xmpi_comm* c, const char* name, long value) {
-  if (!c || c->finalized || !name) return XMPI_ERR_STATE;
-  std::lock_guard<std::mutex> g(c->coll_mu);
-  const std::string n = name;
-  if (n == "channels") c->channels = std::max<long>(0, value);
-  else if (n == "piece_bytes") c->piece_bytes = std::max<long>(0, value);
-  else if (n == "copy_engine") c->copy_engine = value ? 1 : 0;
-  else if (n == "timeout_s") c->timeout_s = value;
-  else if (n == "prof_every") c->prof_every = std::max<long>(1, value);
-  else if (n == "batch_copies") c->batch_copies = value ? 1 : 0;
-  else if (n == "oneshot_bytes") c->oneshot_bytes = std::max<long>(0, value);
-  else if (n == "zero_copy") c->zero_copy = value ? 1 : 0;
-  else if (n == "zc_bcast_push_bytes") c->zc_bcast_push_bytes = std::max<long>(0, value);
-  else if (n == "zc_group_launch") c->zc_group_launch = value ? 1 : 0;
-  else if (n == "p2p_direct_bytes") c->p2p_direct_bytes = value;  // < 0: always through the mail slots
-  else if (n == "p2p_kernel_ack") c->p2p_kernel_ack = value ? 1 : 0;
-  else if (n == "p2p_agent_us") c->p2p_agent_us = std::max<long>(0, value);
-  else if (n == "dsync") c->dsync = value ? 1 : 0;
-  else if (n == "dsync_grid") c->dsync_grid_cap = std::max<long>(0, value);
-  else if (n == "dsync_unroll") c->dsync_unroll = std::max<long>(1, std::min<long>(2, value));
-  else if (n == "dsync_tiles") c->dsync_tiles = std::max<long>(1, value);
-  else if (n == "p2p_grid_cap") c->p2p_grid_cap = std::max<long>(0, std::min<long>(value, 4096));
-  else if (n == "ll_bytes") c->ll_bytes = std::max<long>(0, std::min<long>((long)kLLMaxPayload, value));  // untuned AUTO: LL lines up to here
-  else if (n == "agent_ll") c->agent_ll = value < 0 ? 0 : std::min<long>(value, 2);  // blocking LL collectives by the lingering agent (no launch); (2 = 1)
-  else if (n == "ll_agent_us") c->ll_agent_us = std::max<long>(0, value);
-  else if (n == "agent_ll_bytes") c->agent_ll_bytes = std::max<long>(0, std::min<long>((long)kLLMaxPayload, value));
-  else if (n == "dsync_split_bytes") c->dsync_split_bytes = std::max<long>(0, value);  // 0: always one kernel
-  else if (n == "xcd_check") c->xcd_check = value ? 1 : 0;
-  else if (n == "body_sys") c->body_sys = value ? 1 : 0;
-  else if (n == "xcds") c->xcds = (int)std::max<long>(0, std::min<long>(value, 32));  // (tests: a GPU with more XCDs than it has)
-  else if (n == "sched_channels") c->sched_channels = std::max<long>(0, value);
-  else if (n == "sched_grid") c->sched_grid = std::max<long>(0, value);
-  else if (n == "tree_piece_bytes") c->tree_piece_bytes = std::max<long>(4096, value);
-  else if (n == "tuned") c->tuned = value != 0;  // 0: AUTO forgets the table of xmpi_tune
-  else if (n == "tune_mask") c->tune_mask = value;  // bit k = 0: xmpi_tune leaves candidate k out (1 other unroll, 2 meet / body / done,
-                                                    // 3 push-only, 4 ring kernel, 5 halving kernel, 6 LL lines, 7 ring kernel push form,
-                                                    // 8 halving kernel push form, 9 tree kernel, 10 tree kernel push form); the default
-                                                    // form always runs
-  else if (n.rfind("tune_", 0) == 0) {  // tune_<algo|split|unroll>_<collective 0..3>_<size class>: a row of the table AUTO follows once
-                                        // "tuned" is 1 -- xmpi_tune's to write; a benchmark or a test standing in for it may
-    int coll = -1, cls = -1;
-    char what[16] = {0};
-    if (sscanf(name, "tune_%15[a-z]_%d_%d", what, &coll, &cls) != 3 || coll < 0 || coll >= 4 || cls < 0 || cls >= xmpi_comm::kTuneClasses ||
-        value < -1 || value >= XMPI_ALGO_COUNT)
-      return XMPI_ERR_ARG;
-    const std::string w = what;
-    if (w == "algo") c->tune_algo[coll][cls] = (int8_t)value;
-    else if (w == "split") c->tune_split[coll][cls] = (int8_t)value;
-    else if (w == "unroll") c->tune_unroll[coll][cls] = (int8_t)value;
-    else return XMPI_ERR_ARG;
-  }
-  else if (n == "kernel_mode") set_kernel_mode((int)value);  // process-wide
-  else if (n == "grid_cap") set_grid_cap((int)value);        // process-wide
-  else return XMPI_ERR_ARG;
-  return XMPI_OK;
-}
-
-long xmpi_get_param(const xmpi_comm* c, const char* name) {
-  if (!c || c->finalized || !name) return -1;
-  const std::string n = name;
-  if (n == "channels") return c->channels;
-  if (n == "piece_bytes") return c->piece_bytes;
-  if (n == "copy_engine") return c->copy_engine;
-  if (n == "timeout_s") return c->timeout_s;
-  if (n == "watchdog_ms") return c->watchdog_ms;
-  if (n == "dead_rank") return c->ctl->dead_rank();  // the first rank whose process the watchdog found gone; -1 = none
-  if (n == "zero_copy") return c->zero_copy;
-  if (n == "heap_arenas" || n == "heap_reserved" || n == "heap_in_use") {
-    size_t a = 0, r = 0, u = 0;
-    heap_stats(c->device, &a, &r, &u);
-    return (long)(n == "heap_arenas" ? a : n == "heap_reserved" ? r : u);
-  }
-  if (n == "hbm_free_mib" || n == "hbm_total_mib") {  // of this rank's GPU, as the runtime reports it
-    size_t fr = 0, tot = 0;
-    if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) return -1;
-    return (long)((n == "hbm_free_mib" ? fr : tot) >> 20);
-  }
-  if (n == "p2p_direct_bytes") return c->p2p_direct_bytes;
-  if (n == "p2p_kernel_ack") return c->p2p_kernel_ack;
-  if (n == "p2p_agent_us") return c->p2p_agent_us;
-  if (n == "p2p_agent_served") return (long)c->p2p_agent_served;
-  if (n == "p2p_agent_launches") return (long)c->p2p_agent_launches;
-  if (n == "dsync") return dsync_usable(c) ? 1 : 0;
-  if (n == "dsync_epoch") return (long)c->dsync_epoch;
-  if (n == "dsync_launches") return (long)c->dsync_launches;
-  if (n == "dsync_bounced") return (long)c->dsync_bounced;
-  if (n == "dsync_sharers") return c->dsync_sharers;
-  if (n == "dsync_sharers_job") return c->dsync_sharers_job;
-  if (n == "dsync_unroll") return c->dsync_unroll;
-  if (n == "dsync_tiles") return c->dsync_tiles;
-  if (n == "p2p_grid_cap") return c->p2p_grid_cap;
-  if (n == "ll_bytes") return c->ll_bytes;
-  if (n == "ll_max_bytes") return (long)kLLMaxPayload;
-  if (n == "dsync_ll_launches") return (long)c->dsync_ll_launches;
-  if (n == "dsync_v_launches") return (long)c->dsync_v_launches;
-  if (n == "agent_ll") return c->agent_ll;
-  if (n == "agent_ll_bytes") return c->agent_ll_bytes;
-  if (n == "ll_agent_us") return c->ll_agent_us;
-  if (n == "dsync_ll_agent") return (long)c->dsync_ll_agent;
-  if (n == "ll_agent_launches") return (long)c->ll_agent_launches;
-  if (n == "agent_ll_wait_ns") return (long)c->agent_ll_wait_ns;  // command written -> answer seen, summed over dsync_ll_agent calls
-  if (n == "dsync_grid") return c->dsync_grid_cap;
-  if (n == "dsync_split_bytes") return c->dsync_split_bytes;
-  if (n == "roctx") return roctx_enabled() ? 1 : 0;  // named ranges for the profilers are on (trace.h)
-  if (n == "xcd_check") return c->xcd_check;
-  if (n == "body_sys") return c->body_sys;
-  if (n == "xcds") return c->xcds;
-  if (n == "xcd_probe_mask") return (long)c->xcd_probe_mask;
-  if (n == "xcd_short") return (long)c->xcd_short;
-  if (n == "xcd_meet_mask") return c->dsync_status ? (long)__atomic_load_n(c->dsync_status + 6, __ATOMIC_RELAXED) : -1;
-  if (n == "xcd_done_mask") return c->dsync_status ? (long)__atomic_load_n(c->dsync_status + 7, __ATOMIC_RELAXED) : -1;
-  if (n == "dsync_split_launches") return (long)c->dsync_split_launches;
-  if (n == "dsync_sched_launches") return (long)c->dsync_sched_launches;
-  if (n == "dsync_land_bytes") return (long)c->dsync_land_bytes;
-  // what xmpi_init's vote left the job with: 0 = everything; bit 0 (1): the split form's data kernel runs at system scope (the XCD
-  // probe of THIS rank's GPU); bit 1 (2): the ranks meet on the host (some flag page could not be allocated, exported or mapped);
-  // bit 2 (4): no windows (some window could not be mapped: no staged step tables, no mail slots); bit 3 (8): a schedule gave wrong
-  // answers when the library checked it here and was taken out (tune_rejected).  xmpi_degraded() says why.
-  if (n == "degraded") {
-    bool shared_gpu = false;  // (ranks hosted by threads of one process on one GPU meet on the host by design, not by degradation)
-    for (int p = 0; p < c->size; p++) shared_gpu = shared_gpu || c->peer_coloc[p];
-    // (... and so do more ranks than the device side is sized for)
-    return (c->body_sys == 1 && c->dsync_ok ? 1 : 0) | ((c->size > 1 && c->size <= kDsyncRanks && c->dsync && !c->dsync_ok && !shared_gpu) ? 2 : 0) | (c->windows_ok ? 0 : 4) |
-           (c->rejected_why.empty() ? 0 : 8);
-  }
-  if (n == "windows_ok") return c->windows_ok ? 1 : 0;
-  if (n == "sched_channels") return c->sched_channels;
-  if (n == "sched_grid") return c->sched_grid;
-  if (n == "tree_piece_bytes") return c->tree_piece_bytes;
-  if (n == "tuned") return c->tuned ? 1 : 0;
-  if (n == "tune_mask") return c->tune_mask;
-  // schedules whose answers the library found wrong on this machine (xmpi_tune, xmpi_init's self-check): how many in all, and per
-  // collective (0 allreduce, 1 allgather, 2 bcast, 3 reduce) a bit per candidate -- the numbering of tune_mask
-  if (n == "tune_rejected") return __builtin_popcount(c->tune_rejected[0]) + __builtin_popcount(c->tune_rejected[1]) + __builtin_popcount(c->tune_rejected[2]) + __builtin_popcount(c->tune_rejected[3]);
-  if (n.rfind("tune_rejected_", 0) == 0) {
-    const int coll = atoi(name + 14);
-    return (coll >= 0 && coll < 4 && name[14] >= '0' && name[14] <= '3' && !name[15]) ? (long)c->tune_rejected[coll] : -1;
-  }
-  if (n == "selfcheck") return c->selfcheck;
-  if (n == "p2p_rejected") return (long)c->p2p_rejected;  // the self-check's verdict on Send / Receive: bit 0 the direct pull (-> mail slots), bit 1 everything
-  if (n == "init_selfcheck_ms") return c->selfcheck_ms < 0 ? -1 : (long)(c->selfcheck_ms + 0.999);  // xmpi_init's self-check: -1 = did not run
-  if (n == "init_selfcheck_us") return c->selfcheck_ms < 0 ? -1 : (long)(c->selfcheck_ms * 1e3);
-  if (n == "init_selfcheck_setup_us") return c->selfcheck_ms < 0 ? -1 : (long)(c->selfcheck_setup_ms * 1e3);  // ... of which: its buffers (the job's first arena, the first kernel's code object)
-  if (n == "tune_us") return (long)(c->tune_ms * 1e3);              // the last xmpi_tune, all of it
-  if (n == "tune_check_us") return (long)(c->tune_check_ms * 1e3);  // ... the part spent checking answers (expected results, poison, compare)
-  if (n.rfind("tune_", 0) == 0) {  // tune_<algo|split|unroll>_<collective 0..3>_<size class>: the table of xmpi_tune
-    int coll = -1, cls = -1;
-    char what[16] = {0};
-    if (sscanf(name, "tune_%15[a-z]_%d_%d", what, &coll, &cls) == 3 && coll >= 0 && coll < 4 && cls >= 0 && cls < xmpi_comm::kTuneClasses) {
-      const std::string w = what;
-      if (w == "algo") return c->tune_algo[coll][cls];
-      if (w == "split") return c->tune_split[coll][cls];
-      if (w == "unroll") return c->tune_unroll[coll][cls];
-    }
-    return -1;
-  }
-  if (n.rfind("prof_min_ns_", 0) == 0 || n.rfind("prof_max_ns_", 0) == 0) {  // the shortest / longest sampled launch of kind 0..4 since xmpi_prof_reset
-    const int kind = name[12] - '0';
-    if (kind < 0 || kind >= PROF_KINDS || name[13]) return -1;
-    return (long)((n[6] == 'i' ? c->prof[kind].min_ms : c->prof[kind].max_ms) * 1e6);
-  }
-  if (n == "p2p_direct_count") return (long)c->p2p_direct_count;
-  if (n == "p2p_staged_count") return (long)c->p2p_staged_count;
-  if (n == "p2p_lane_count") return (long)c->p2p_lane_count;
-  if (n == "host_bounce_calls") return (long)c->host_bounce_calls;
-  if (n == "host_lane_bytes") return (long)c->ctl->host_lane_bytes();
-  if (n == "zc_seq") return (long)c->zc_seq;
-  if (n == "zc_fallbacks_unregistered") return (long)c->zc_fallbacks_unregistered;
-  if (n == "zc_fallbacks_unmappable") return (long)c->zc_fallbacks_unmappable;
-  if (n == "shared_stream") return c->shared_stream ? 1 : 0;
-  if (n == "kernel_mode") return get_kernel_mode();
-  if (n == "grid_cap") return get_grid_cap();
-  if (n == "last_run_us") return (long)c->last_run_us;
-  if (n == "last_sync_us") return (long)c->last_sync_us;
-  if (n == "lanes") return c->lanes;
-  if (n == "fifo_depth") return c->fifo_depth;
-  if (n == "slot_bytes") return (long)c->slot_bytes;
-  if (n == "p2p_slot_bytes") return (long)c->p2p_slot_bytes;
-  if (n == "window_bytes") return (long)c->window_bytes;
-  if (n == "ring_channels_max") return ring_channel_count(c->size) * c->lanes;
-  if (n == "ring_channels") return ring_channel_count(c->size);
-  return -1;
-}
 
 }  // extern "C"

@@ -173,7 +173,7 @@ struct xmpi_comm {
   int8_t tune_algo[4][kTuneClasses];       // [collective][class]: an xmpi_algo, or -1 = not tuned (built-in rule)
   int8_t tune_split[4][kTuneClasses];      // 1 = split form, 0 = one kernel, -1 = by dsync_split_bytes
   int8_t tune_unroll[4][kTuneClasses];
-  bool tuned = false;
+  long tuned = 0;  // AUTO follows the table (xmpi_tune sets it; xmpi_set_param "tuned")
   long tune_mask = -1;  // candidates xmpi_tune may time (bit per candidate; see xmpi_set_param "tune_mask")
   // The candidates by number: what tune_mask and tune_rejected_<collective> name bit by bit.
   enum { CAND_FOLD = 0, CAND_FOLD_U2 = 1, CAND_SPLIT = 2, CAND_ZPUSH = 3, CAND_RING = 4, CAND_RHD = 5, CAND_LL = 6, CAND_RING_PUSH = 7,
@@ -195,7 +195,7 @@ struct xmpi_comm {
   double tune_ms = 0, tune_check_ms = 0;  // the last xmpi_tune: all of it / the part spent checking answers
   uint32_t* dsync_status = nullptr;          // pinned host word a kernel writes its first failure to ...
   uint32_t* dsync_status_dev = nullptr;      // ... and its device address
-  int xcds = 0;                  // XCDs of this rank's GPU as a 1024-block probe grid found them (0: not probed)
+  long xcds = 0;                 // XCDs of this rank's GPU as a 1024-block probe grid found them (0: not probed)
   uint32_t xcd_probe_mask = 0;   // XCDs a grid of kXcdBlocks one-wave blocks reached at start-up (what the meet / done kernels are)
   long xcd_check = 1;            // the split form's done kernel fails the collective when meet or done missed an XCD; XMPI_XCD_CHECK
   long body_sys = 0;             // split form: data kernel with system-scope loads / stores (no L2 assumption); XMPI_BODY_SYS
@@ -348,6 +348,18 @@ bool trace_on();  // XMPI_TRACE=1: one line per bootstrap step on stderr (where 
     if (::xmpi::trace_on()) fprintf(stderr, "[xmpi %d %.6f] %s\n", (rank), ::xmpi::now_seconds(), (what)); \
   } while (0)
 long env_long(const char* name, long dflt);
+// params.cpp: the one table of knobs.  What the environment says about the row of variable `env`, brought into the row's range;
+// with the default the caller computed, for a row whose default waits for the job's layout.  params_from_env: every other row.
+constexpr long kRowDefault = -0x7fffffffffffffffl - 1;
+// (hidden: what the library exports stays what it was, plus xmpi_param_info)
+__attribute__((visibility("hidden"))) long param_env(const char* env, long dflt = kRowDefault);
+__attribute__((visibility("hidden"))) void params_from_env(xmpi_comm* c);
+// every peer is a thread of this process on this GPU (with shared_stream: one in-order stream, nothing to overlap)
+inline bool all_peers_colocated(const xmpi_comm* c) {
+  for (int p = 0; p < c->size; p++)
+    if (p != c->rank && !c->peer_coloc[p]) return false;
+  return true;
+}
 inline int use_device(const xmpi_comm* c) {
   // HIP's current device is per OS thread and cgo moves goroutines between threads
   XMPI_HIP(hipSetDevice(c->device));

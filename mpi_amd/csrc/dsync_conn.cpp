@@ -253,7 +253,7 @@ int dsync_connect(xmpi_comm* c, double timeout_s) {
     if (c->body_sys < 0) c->body_sys = (c->xcds > 0 && !covered) ? 1 : 0;
     if (c->xcds > 0 && !covered)
       fprintf(stderr, "xmpi: rank %d: a %d-block grid reaches XCDs %#x of %d -- split collectives use system-scope loads / stores\n",
-              c->rank, kXcdBlocks, c->xcd_probe_mask, c->xcds);
+              c->rank, kXcdBlocks, c->xcd_probe_mask, (int)c->xcds);
   }
   if (c->body_sys < 0) c->body_sys = 0;
   // epochs of this communicator: above whatever earlier communicators left in ANY rank's (pooled, uncleared) page;

@@ -1,8 +1,6 @@
 // init.cpp -- xmpi_init, xmpi_finalize and the one list of what a communicator owns.
 #include <unistd.h>
 
-#include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -87,48 +85,15 @@ int pick_device(int rank, int size, int* device, xmpi_comm** out) {
   return XMPI_OK;
 }
 
-// what the environment says about the communicator itself (the job's layout: join_job; what depends on the layout: where it is known)
-void read_env(xmpi_comm* c) {
-  c->timeout_s = std::max<long>(0, env_long("XMPI_TIMEOUT_S", 0));
-  c->channels = env_long("XMPI_CHANNELS", 0);  // 0 = one ring channel per available link direction
-  c->piece_bytes = env_long("XMPI_PIECE_BYTES", 0);
-  c->copy_engine = env_long("XMPI_COPY_ENGINE", 0);
-  c->batch_copies = env_long("XMPI_BATCH_COPIES", 1) ? 1 : 0;
-  c->oneshot_bytes = std::max<long>(0, env_long("XMPI_ONESHOT_BYTES", 1 << 20));
-  c->zero_copy = env_long("XMPI_ZERO_COPY", 1) ? 1 : 0;
-  c->zc_bcast_push_bytes = std::max<long>(0, env_long("XMPI_ZC_BCAST_PUSH_BYTES", 256 << 10));
-  c->zc_group_launch = env_long("XMPI_ZC_GROUP_LAUNCH", 1) ? 1 : 0;
-  c->p2p_direct_bytes = env_long("XMPI_P2P_DIRECT_BYTES", 1);
-  if (getenv("XMPI_KERNEL_MODE")) set_kernel_mode((int)env_long("XMPI_KERNEL_MODE", -1));
-  if (getenv("XMPI_GRID_CAP")) set_grid_cap((int)env_long("XMPI_GRID_CAP", 0));
-  c->dsync = env_long("XMPI_DSYNC", 1) ? 1 : 0;
-  c->dsync_split_bytes = std::max<long>(0, env_long("XMPI_DSYNC_SPLIT_BYTES", 4 << 20));
-  c->xcd_check = env_long("XMPI_XCD_CHECK", 1) ? 1 : 0;
-  c->body_sys = env_long("XMPI_BODY_SYS", -1);  // -1: decided by the XCD probe (dsync_prepare)
-  c->ll_bytes = env_long("XMPI_LL_BYTES", -1);  // -1: decided when the job's layout is known (dsync_connect)
-  c->agent_ll = std::max<long>(0, std::min<long>(env_long("XMPI_AGENT_LL", 1), 2));
-  c->agent_ll_bytes = std::max<long>(0, std::min<long>((long)kLLMaxPayload, env_long("XMPI_AGENT_LL_BYTES", 8192)));
-  c->sched_channels = std::max<long>(0, env_long("XMPI_SCHED_CHANNELS", 0));
-  c->sched_grid = std::max<long>(0, env_long("XMPI_SCHED_GRID", 0));
-  c->tree_piece_bytes = std::max<long>(4096, env_long("XMPI_TREE_PIECE_BYTES", 256 << 10));
-  c->dsync_grid_cap = std::max<long>(0, env_long("XMPI_DSYNC_GRID", 0));
-  c->p2p_kernel_ack = env_long("XMPI_P2P_KERNEL_ACK", 1) ? 1 : 0;
-  c->p2p_agent_us = std::max<long>(0, env_long("XMPI_P2P_AGENT_US", 40));
-  c->ll_agent_us = std::max<long>(0, env_long("XMPI_LL_AGENT_US", c->p2p_agent_us));
-  c->p2p_grid_cap = std::max<long>(0, std::min<long>(env_long("XMPI_P2P_GRID_CAP", 0), 4096));
-  c->watchdog_ms = std::max<long>(0, env_long("XMPI_WATCHDOG_MS", 50));
-  c->selfcheck = env_long("XMPI_SELFCHECK", -1);
-}
-
 // the control block: rank 0's layout is the job's.  Nothing to give back when this fails.
 int join_job(int rank, int size, int device, const char* job_key, double limit, xmpi_comm** out) {
   CtlConfig cfg;
-  cfg.lanes = (int32_t)std::min<long>(kMaxLanes, std::max<long>(1, env_long("XMPI_LANES", 2)));
-  cfg.fifo_depth = (int32_t)std::min<long>(64, std::max<long>(2, env_long("XMPI_FIFO_DEPTH", 8)));
-  cfg.slot_bytes = (uint64_t)std::max<long>(4096, env_long("XMPI_SLOT_BYTES", 8l << 20)) / 256 * 256;
-  cfg.p2p_depth = (int32_t)std::min<long>(16, std::max<long>(2, env_long("XMPI_P2P_DEPTH", 2)));
-  cfg.p2p_slot_bytes = (uint64_t)std::max<long>(4096, env_long("XMPI_P2P_SLOT_BYTES", 4l << 20)) / 256 * 256;
-  cfg.host_lane_bytes = env_long("XMPI_HOST_LANES", 1) ? 1 : 0;  // a request: the creator of the block sizes and reserves them
+  cfg.lanes = (int32_t)param_env("XMPI_LANES");
+  cfg.fifo_depth = (int32_t)param_env("XMPI_FIFO_DEPTH");
+  cfg.slot_bytes = (uint64_t)param_env("XMPI_SLOT_BYTES") / 256 * 256;
+  cfg.p2p_depth = (int32_t)param_env("XMPI_P2P_DEPTH");
+  cfg.p2p_slot_bytes = (uint64_t)param_env("XMPI_P2P_SLOT_BYTES") / 256 * 256;
+  cfg.host_lane_bytes = param_env("XMPI_HOST_LANES");  // a request: the creator of the block sizes and reserves them
   XMPI_TRACE_STEP(rank, "init: joining the control block");
   std::string key = (job_key && *job_key) ? job_key : "default";
   std::string err;
@@ -155,7 +120,8 @@ int join_job(int rank, int size, int device, const char* job_key, double limit, 
   memset(c->tune_algo, -1, sizeof c->tune_algo);
   memset(c->tune_split, -1, sizeof c->tune_split);
   memset(c->tune_unroll, 0, sizeof c->tune_unroll);
-  read_env(c);
+  params_from_env(c);  // every row of the table (params.cpp) whose default does not wait for the job's layout; those: where it is known
+  c->ll_agent_us = param_env("XMPI_LL_AGENT_US", c->p2p_agent_us);
   *out = c;
   return XMPI_OK;
 }
@@ -256,7 +222,7 @@ int choose_streams(xmpi_comm* c) {
       colocated = true;
       c->peer_coloc[p] = true;
     }
-  const long shared_env = env_long("XMPI_SHARED_STREAM", -1);
+  const long shared_env = param_env("XMPI_SHARED_STREAM");
   c->shared_stream = shared_env < 0 ? colocated : shared_env != 0;
   if (!c->shared_stream) return XMPI_OK;
   hipStream_t s = shared_stream_for(c->device);
@@ -313,10 +279,10 @@ int connect_and_meet(xmpi_comm* c, double limit) {
   ctl->set_watch(c->watchdog_ms > 0);
   dsync_start_helper(c);
   XMPI_TRACE_STEP(c->rank, "init: final barrier");
-  c->dsync_unroll = env_long("XMPI_DSYNC_UNROLL", c->dsync_sharers > 1 ? 1 : 2);
+  c->dsync_unroll = param_env("XMPI_DSYNC_UNROLL", c->dsync_sharers > 1 ? 1 : 2);
   // ranks sharing a GPU: fewer, longer blocks (8 processes on one MI355X: 4 MiB 170 -> 90 us, 16 MiB 231 -> 169 us);
   // a rank with a GPU to itself keeps one tile per block -- over links more waves in flight is what hides latency
-  c->dsync_tiles = std::max<long>(1, env_long("XMPI_DSYNC_TILES", c->dsync_sharers > 1 ? 8 : 1));
+  c->dsync_tiles = param_env("XMPI_DSYNC_TILES", c->dsync_sharers > 1 ? 8 : 1);
   if (hipMalloc((void**)&c->dev_words, 4 * sizeof(uint64_t)) != hipSuccess) {
     hip_fail(hipGetLastError(), "hipStreamCreate/hipMalloc", __FILE__, __LINE__);
     return XMPI_ERR_HIP;

@@ -70,6 +70,7 @@ SYMBOLS = [
     ("xmpi_fill_pattern", _I, [_P, _P, _Z, _I, _I, C.c_uint64]),
     ("xmpi_set_param", _I, [_P, C.c_char_p, _L]),
     ("xmpi_get_param", _L, [_P, C.c_char_p]),
+    ("xmpi_param_info", _I, [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
     ("xmpi_prof_enable", _I, [_P, _I]),
     ("xmpi_prof_reset", _I, [_P]),
     ("xmpi_prof_get", _I, [_P, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -463,6 +464,7 @@ class Comm:
 
     def copy_local_pairs(self, dsts: Sequence, srcs: Sequence, nbytes: int) -> None:
         """dsts[k] = srcs[k] in one launch with the fold's access pattern (reduce_local_multi without the arithmetic)"""
+        assert len(dsts) == len(srcs) <= 16, "copy_local_pairs: as many destinations as sources, at most 16"
         d = (_P * len(dsts))(*[_ptr(x) for x in dsts])
         s_ = (_P * len(srcs))(*[_ptr(x) for x in srcs])
         _check(lib().xmpi_copy_local_pairs(self.handle, d, s_, len(srcs), nbytes), "xmpi_copy_local_pairs")

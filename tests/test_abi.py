@@ -66,33 +66,76 @@ def test_every_declared_entry_of_the_boundary_header_cites_the_reference_or_says
     assert seen >= 60
 
 
-def test_every_knob_is_in_the_table():
-    """INTEGRATION.md section 5 is THE table of environment variables and xmpi_set_param names: what the product code reads
-    (getenv / env_long / env_size) or accepts (xmpi_set_param) must have a row, and a row must name something the code reads"""
-    import glob
-    import re
+def knob_section():
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    sec = doc[doc.index("## 5. Every knob"):]
-    rows = [ln for ln in sec.splitlines() if ln.startswith("| `XMPI_") or ln.startswith("| — |")]
-    env_doc = set(re.findall(r"`(XMPI_[A-Z0-9_]+)`", "\n".join(ln.split("|")[1] for ln in rows)))
-    par_doc = set(re.findall(r"`([a-z0-9_]+)`", "\n".join(ln.split("|")[2] for ln in rows)))
+    return doc[doc.index("## 5. Every knob"):]
+
+
+def knob_rows():
+    """the rows of INTEGRATION.md section 5's table: (environment variables, xmpi_set_param names, the default cell)"""
+    rows = [ln.split("|") for ln in knob_section().splitlines() if ln.startswith("| `XMPI_") or ln.startswith("| — |")]
+    return [(set(re.findall(r"`(XMPI_[A-Z0-9_]+)`", r[1])), set(re.findall(r"`([a-z0-9_]+)`", r[2])), r[3].strip()) for r in rows]
+
+
+def param_table():
+    """the library's own table (mpi_amd/csrc/params.cpp) through xmpi_param_info: (name, variable, default, lo, hi, flags) per row"""
+    L, rows = xmpi.lib(), []
+    while True:
+        name, env, d, lo, hi, fl = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_long(), ctypes.c_long(), ctypes.c_long(), ctypes.c_int()
+        if L.xmpi_param_info(len(rows), ctypes.byref(name), ctypes.byref(env), ctypes.byref(d), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(fl)) != xmpi.OK:
+            assert L.xmpi_param_info(len(rows), None, None, None, None, None, None) == xmpi.ERR_ARG and L.xmpi_param_info(-1, None, None, None, None, None, None) == xmpi.ERR_ARG
+            return rows
+        rows.append((name.value.decode() if name.value else None, env.value.decode() if env.value else None, d.value, lo.value, hi.value, fl.value))
+
+
+WRITABLE, BOOLEAN, LAYOUT_DEFAULT, READ_ONLY, PATTERN = 1, 2, 4, 8, 16
+
+
+def _default_cell(cell):
+    """a plain integer, or N KiB / MiB / GiB; None: neither"""
+    m = re.fullmatch(r"(-?\d+)(?: (KiB|MiB|GiB))?", cell)
+    return int(m.group(1)) << {None: 0, "KiB": 10, "MiB": 20, "GiB": 30}[m.group(2)] if m else None
+
+
+def test_every_knob_is_in_the_table():
+    """INTEGRATION.md section 5 is THE table of environment variables and xmpi_set_param names, held to the library's own table
+    (xmpi_param_info) and, for the process-wide variables read where they are used, to the sources (getenv / env_long / env_size):
+    names and variables both ways, every readable name, and the default of every row that has a fixed one"""
+    import glob
+    sec, doc, table = knob_section(), knob_rows(), param_table()
+    env_doc = set().union(*(envs for envs, _, _ in doc))
+    par_doc = set().union(*(names for _, names, _ in doc))
     src = ""
     for pat in ("mpi_amd/csrc/*.cpp", "mpi_amd/csrc/*.h", "mpi_amd/csrc/*.hip", "mpi_amd/host/*.cpp", "mpi_amd/host/*.hpp", "launcher/*.cpp"):
         for f in glob.glob(os.path.join(ROOT, pat)):
             src += open(f).read()
-    env_code = set(re.findall(r"(?:getenv|env_long|env_size)\(\s*\"(XMPI_[A-Z0-9_]+)\"", src))
+    env_code = {r[1] for r in table if r[1]} | set(re.findall(r"(?:getenv|env_long|env_size)\(\s*\"(XMPI_[A-Z0-9_]+)\"", src))
     assert env_code - env_doc == set(), f"read by the code, missing from INTEGRATION.md section 5: {sorted(env_code - env_doc)}"
     assert env_doc - env_code == set(), f"in the table, read by nothing: {sorted(env_doc - env_code)}"
-    api = open(os.path.join(ROOT, "mpi_amd", "csrc", "api.cpp")).read()
-    setter = api[api.index("int xmpi_set_param("):api.index("long xmpi_get_param(")]
-    par_code = set(re.findall(r'n == "([a-z0-9_]+)"', setter))
+    par_code = {r[0] for r in table if r[5] & WRITABLE and not r[5] & PATTERN}
     assert par_code - par_doc == set(), f"accepted by xmpi_set_param, missing from the table: {sorted(par_code - par_doc)}"
     assert par_doc - par_code == set(), f"in the table, not accepted by xmpi_set_param: {sorted(par_doc - par_code)}"
-    getter = api[api.index("long xmpi_get_param("):api.index("int xmpi_tune_decide(") if "int xmpi_tune_decide(" in api else len(api)]
-    getter = getter[:getter.index("\n}\n")]
-    for name in set(re.findall(r'n == "([a-z0-9_]+)"', getter)):
-        assert f"`{name}`" in sec, f"xmpi_get_param(\"{name}\") is not in INTEGRATION.md section 5"
+    for r in table:
+        assert bool(r[5] & WRITABLE) != bool(r[5] & READ_ONLY), r
+        if r[0]:  # (a family of names: `prefix<what>`)
+            assert (f"`{r[0]}" if r[5] & PATTERN else f"`{r[0]}`") in sec, f"xmpi_get_param(\"{r[0]}\") is not in INTEGRATION.md section 5"
     assert len(env_code) < 60, "knob sprawl"
+    # the default cell of every row the library's table knows: equal to the table's, or no fixed default there
+    by_env, by_name = {r[1]: r for r in table if r[1]}, {r[0]: r for r in table if r[0]}
+    skipped, checked = set(), 0
+    for envs, names, cell in doc:
+        rows = {by_env[e] for e in envs if e in by_env} | {by_name[n] for n in names if n in by_name}
+        assert len(rows) <= 1, f"{envs} {names}: one row here, {len(rows)} in the library's table"
+        for r in rows:
+            assert ({r[1]} if r[1] else set()) == envs and ({r[0]} if r[5] & WRITABLE else set()) == names, f"{envs} {names}: the library's row is {r[:2]}"
+            if r[5] & LAYOUT_DEFAULT:
+                skipped.add(r)
+                continue
+            assert _default_cell(cell) is not None, f"{envs} {names}: the default cell '{cell}' is neither an integer nor N KiB / MiB / GiB"
+            assert _default_cell(cell) == r[2], f"{envs} {names}: default {cell} here, {r[2]} in the library's table"
+            checked += 1
+    assert skipped == {r for r in table if r[5] & LAYOUT_DEFAULT}, "the rows without a fixed default are not the ones the library flags"
+    assert checked >= 35 and len(skipped) == 4, (checked, len(skipped))
 
 
 def _split_args(text):

@@ -30,6 +30,19 @@ type Personal interface {
 	Alltoall(send, recv interface{}) error
 }
 
+// The reduction operators a Collective / Personal backend takes as `op`: the values of xmpi_op (include/xmpi.h), which
+// xgmi.Sum ... xgmi.BXor share.  OpBAnd / OpBOr / OpBXor are bitwise and defined for integer element types only.
+const (
+	OpSum = iota
+	OpProd
+	OpMin
+	OpMax
+	OpSumWide
+	OpBAnd
+	OpBOr
+	OpBXor
+)
+
 var errNoCollectives = errors.New("mpi: the registered implementation provides no collectives")
 
 // Bcast replicates root's buffer on every rank.

@@ -67,6 +67,11 @@ const (
 	// SumWide: F16 / BF16 accumulated in f32 in rank order and rounded once; Sum for every other type.  Schedules that pass
 	// partial sums between ranks (ring, halving, tree) refuse it.
 	SumWide
+	// BAnd, BOr, BXor: the bitwise reductions, for U8 / I32 / I64 only (a float type is an argument error on every rank); exact, so
+	// every schedule gives the same bits.
+	BAnd
+	BOr
+	BXor
 )
 
 // DeviceBuffer is a typed span of this rank's HBM; it is what `data interface{}` carries on the

@@ -58,14 +58,26 @@ typedef enum {
  * Where it runs: every schedule in which all N contributions to an element meet in one lane -- AUTO, ZCOPY, ZPUSH, LL, DIRECT, the
  * stream-ordered and captured forms, xmpi_reduce_local_n / _multi.  RING, RHD, TREE and their PUSH forms NAMED BY THE CALLER answer
  * XMPI_ERR_UNSUPPORTED on every rank, before anything is announced: their partial sums travel between ranks in the 16-bit type, so
- * there is nothing wide to accumulate in.  AUTO whose tuned table names one of them runs the fold instead. */
+ * there is nothing wide to accumulate in.  AUTO whose tuned table names one of them runs the fold instead.
+ * XMPI_BAND / XMPI_BOR / XMPI_BXOR (no counterpart in the reference either) are the bitwise reductions: for XMPI_U8, XMPI_I32 and
+ * XMPI_I64, element i of the result is the bitwise AND / OR / XOR of element i of every contribution -- flag words merged, capability
+ * masks intersected, a parity over the ranks' buffers.  Signedness plays no part; with a single contribution the element is copied.
+ * They are exact, associative and commutative, so every schedule name the collective accepts gives the same bits: AUTO, ZCOPY, ZPUSH,
+ * LL, DIRECT, RING, RHD, TREE and the PUSH forms, the stream-ordered, captured, non-blocking and _repeat forms, host slices and
+ * unregistered memory, xmpi_reduce_local and its _n / _multi / _batch forms; routing is by size as for XMPI_MAX.  With XMPI_F16 / F32 /
+ * F64 / BF16 the call is XMPI_ERR_ARG on every rank, from the arguments alone, before anything is announced or launched: the
+ * communicator stays usable and xmpi_last_error says that a bitwise operator needs an integer type.  Ranks passing different ones
+ * are not in the same call (XMPI_ERR_ARG on every rank), like any two operators. */
 typedef enum {
   XMPI_SUM = 0,
   XMPI_PROD = 1,
   XMPI_MIN = 2,
   XMPI_MAX = 3,
   XMPI_SUM_WIDE = 4,
-  XMPI_OP_COUNT = 5,
+  XMPI_BAND = 5,
+  XMPI_BOR = 6,
+  XMPI_BXOR = 7,
+  XMPI_OP_COUNT = 8,
   XMPI_OP_ANY_INT = 0x7fffffff
 } xmpi_op;
 

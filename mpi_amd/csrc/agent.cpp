@@ -179,6 +179,8 @@ int agent_submit_ll(xmpi_comm* c, const void* send, void* recv, size_t bytes, in
     return 0;
   AgentLine line = ll_line(c);
   if (c->ll_agent_running && line.gone()) c->ll_agent_running = false;  // it said it went: started again below
+  static_assert(XMPI_OP_COUNT <= 8, "an LL command names its operator in three bits (kernels.h): a ninth operator needs another layout");
+  static_assert(kAgentLLConsecutiveShift - kAgentLLOpShift == 3, "... and these are the three");
   const uint64_t meta = (uint64_t)(ll_coll & 3) | ((uint64_t)(root & 15) << kAgentLLRootShift) |
                         ((uint64_t)(dtype & 7) << kAgentLLDtypeShift) | ((uint64_t)(op & 7) << kAgentLLOpShift) |
                         ((uint64_t)(consecutive ? 1 : 0) << kAgentLLConsecutiveShift);

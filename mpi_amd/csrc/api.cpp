@@ -215,6 +215,7 @@ static int collective(xmpi_comm* c, int coll, int algo, int root, const void* se
     set_last_error("bad dtype / op / root / algo");
     return XMPI_ERR_ARG;
   }
+  if (refuse_bitwise_on_float(dtype, op)) return XMPI_ERR_ARG;  // a bitwise operator on a float type
   // XMPI_SUM_WIDE: XMPI_SUM for every type but f16 / bf16; there, a stepped schedule the caller names is refused -- its partial sums
   // travel between ranks in the 16-bit type, so no wide accumulator exists.  From the arguments alone: every rank answers alike,
   // before anything is announced or lent.
@@ -512,6 +513,7 @@ static int on_stream(xmpi_comm* c, int coll, int root, const void* sendbuf, void
     set_last_error("bad dtype / op / root");
     return XMPI_ERR_ARG;
   }
+  if (refuse_bitwise_on_float(dtype, op)) return XMPI_ERR_ARG;  // a bitwise operator on a float type
   op = normal_op(dtype, op);
   if (count == 0) return XMPI_OK;
   if (!sendbuf || !recvbuf) {
@@ -718,6 +720,8 @@ int xmpi_iallreduce(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t cou
                     xmpi_request** req) {
   XMPI_ENTER(c);
   if (!req) return XMPI_ERR_ARG;
+  // (a bitwise operator on a float type: refused here, from the arguments, not by the worker)
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   *req = submit(c, [=] { return xmpi_allreduce(c, sendbuf, recvbuf, count, dtype, op, algo); });
   return XMPI_OK;
 }
@@ -741,6 +745,8 @@ int xmpi_ireduce(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count,
                  int algo, xmpi_request** req) {
   XMPI_ENTER(c);
   if (!req) return XMPI_ERR_ARG;
+  // (a bitwise operator on a float type: refused here, from the arguments, not by the worker)
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   *req = submit(c, [=] { return xmpi_reduce(c, sendbuf, recvbuf, count, dtype, op, root, algo); });
   return XMPI_OK;
 }
@@ -768,13 +774,14 @@ int xmpi_request_wait(xmpi_request* r) {
 int xmpi_allreduce_repeat(xmpi_comm* c, const void* sendbuf, void* recvbuf, size_t count, xmpi_dtype dtype, xmpi_op op,
                           int algo, int iters) {
   XMPI_ENTER(c);
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   if (op >= 0 && op < XMPI_OP_COUNT) op = (xmpi_op)normal_op((int)dtype, (int)op);
   // (XMPI_SUM_WIDE on a stepped schedule: refused by collective() below, from the arguments alone)
   const bool wide_stepped = op == XMPI_SUM_WIDE && algo_stepped(algo);
   // Ranks that meet on the device: the steps are ENQUEUED back to back on the communicator's stream and waited for
   // once -- what a stream-ordered caller does, and what the device rendezvous is for (no host round trip per
   // step).  Sampled launches carry their own events, read when the last step has been waited for.
-  const bool on_device = count > 0 && sendbuf && recvbuf && xmpi_dtype_size(dtype) && algo >= 0 && algo < XMPI_ALGO_COUNT && !wide_stepped &&
+  const bool on_device = count > 0 && sendbuf && recvbuf && xmpi_dtype_size(dtype) && op >= 0 && op < XMPI_OP_COUNT && algo >= 0 && algo < XMPI_ALGO_COUNT && !wide_stepped &&
                          dsync_takes(c, COLL_ALLREDUCE, algo) && is_device_pointer(sendbuf) && is_device_pointer(recvbuf);
   if (on_device) {
     drain_worker(c);

@@ -379,6 +379,16 @@ inline int use_device(const xmpi_comm* c) {
 // XMPI_SUM_WIDE is XMPI_SUM for every type but the two 16-bit floats (include/xmpi.h): said once, at the C entry, before a route
 // or a call signature is formed -- a rank passing SUM_WIDE on f32 is in the same call as a rank passing SUM
 inline int normal_op(int dtype, int op) { return (op == XMPI_SUM_WIDE && dtype != XMPI_F16 && dtype != XMPI_BF16) ? (int)XMPI_SUM : op; }
+// XMPI_BAND / XMPI_BOR / XMPI_BXOR are defined for XMPI_U8 / I32 / I64 (include/xmpi.h).  Asked at every entry that takes an operator,
+// beside normal_op: true = the operator is one of the three and the dtype one of the four float types -- xmpi_last_error now says
+// so and the caller answers XMPI_ERR_ARG.  From the arguments alone, so every rank answers alike before anything is announced or
+// launched.  (An operator or a dtype that does not exist is not this function's to refuse: false.)
+inline bool op_is_bitwise(int op) { return op == XMPI_BAND || op == XMPI_BOR || op == XMPI_BXOR; }
+inline bool refuse_bitwise_on_float(int dtype, int op) {
+  if (!op_is_bitwise(op) || !(dtype == XMPI_F16 || dtype == XMPI_F32 || dtype == XMPI_F64 || dtype == XMPI_BF16)) return false;
+  set_last_error("a bitwise operator (XMPI_BAND / XMPI_BOR / XMPI_BXOR) needs an integer type: XMPI_U8, XMPI_I32 or XMPI_I64");
+  return true;
+}
 // the schedules whose partial sums travel between ranks as T: no wide accumulator exists for them
 inline bool algo_stepped(int algo) {
   return algo == XMPI_ALGO_RING || algo == XMPI_ALGO_RHD || algo == XMPI_ALGO_TREE || algo == XMPI_ALGO_RING_PUSH ||

@@ -27,7 +27,11 @@ constexpr int kUnroll = 4;       // 16-byte packets per lane per operand in flig
 enum { DT_U8 = 0, DT_I32 = 1, DT_I64 = 2, DT_F16 = 3, DT_F32 = 4, DT_F64 = 5, DT_BF16 = 6 };
 // OP_SUM_WIDE (XMPI_SUM_WIDE): _Float16 / bf16_t only, and only in the kernels that see all N contributions to an element in one
 // lane (FoldAcc below); the launchers hand it to nothing else (launch.h with_fold_op)
-enum { OP_SUM = 0, OP_PROD = 1, OP_MIN = 2, OP_MAX = 3, OP_SUM_WIDE = 4 };
+// OP_BAND / OP_BOR / OP_BXOR (XMPI_BAND / _BOR / _BXOR): uint8_t, int32_t and int64_t only, in every kernel that has an operator
+// (launch.h with_op hands them on for those three types and for no other)
+enum { OP_SUM = 0, OP_PROD = 1, OP_MIN = 2, OP_MAX = 3, OP_SUM_WIDE = 4, OP_BAND = 5, OP_BOR = 6, OP_BXOR = 7 };
+template <int OP>
+constexpr bool kBitOp = OP == OP_BAND || OP == OP_BOR || OP == OP_BXOR;
 
 struct bf16_t {
   uint16_t bits;
@@ -37,15 +41,30 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 // 16-byte packet: a native vector (not HIP's pack_t struct) so it always lives in 4 VGPRs
 typedef unsigned int pack_t __attribute__((ext_vector_type(4)));
 
+template <typename T>
+constexpr bool kIntegerElem = __is_same(T, uint8_t) || __is_same(T, int32_t) || __is_same(T, int64_t);
+
+// ---- the bitwise operators: on W itself, whatever it holds -- an element, the 8 payload bytes of an LL line (uint64_t), a 16-byte
+// packet (four 32-bit VALU operations: the element width plays no part, nor does signedness)
+template <int OP, typename W>
+__device__ __forceinline__ W bitop(W a, W b) {
+  static_assert(kBitOp<OP>, "AND, OR or XOR");
+  if constexpr (OP == OP_BAND) return (W)(a & b);
+  else if constexpr (OP == OP_BOR) return (W)(a | b);
+  else return (W)(a ^ b);
+}
+
 // ---- scalar combine: one rounding per operation, min/max spelled as in oracle/xmpi_oracle.c ---
 
 template <typename T, int OP>
 __device__ __forceinline__ T combine(T a, T b) {
-  static_assert(OP >= OP_SUM && OP <= OP_MAX, "a two-operand combine has the four operators (the last branch below is MAX)");
+  static_assert((OP >= OP_SUM && OP <= OP_MAX) || kBitOp<OP>, "a two-operand combine has the four arithmetic operators and the three bitwise ones: every branch below names its own");
+  static_assert(!kBitOp<OP> || kIntegerElem<T>, "a bitwise operator is never instantiated with a floating-point type or bf16_t (launch.h with_op)");
   if constexpr (OP == OP_SUM) return a + b;
   else if constexpr (OP == OP_PROD) return a * b;
   else if constexpr (OP == OP_MIN) return (b < a) ? b : a;
-  else return (a < b) ? b : a;
+  else if constexpr (OP == OP_MAX) return (a < b) ? b : a;
+  else return bitop<OP>(a, b);
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
@@ -58,12 +77,12 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 
 template <int OP>
 __device__ __forceinline__ bf16_t combine_bf16(bf16_t a, bf16_t b) {
-  static_assert(OP >= OP_SUM && OP <= OP_MAX, "a two-operand combine has the four operators");
+  static_assert(OP >= OP_SUM && OP <= OP_MAX, "bf16_t has the four arithmetic operators (the bitwise ones are for integer types)");
   float x = bf16_to_f32(a.bits), y = bf16_to_f32(b.bits);
   if constexpr (OP == OP_SUM) return bf16_t{f32_to_bf16(x + y)};
   else if constexpr (OP == OP_PROD) return bf16_t{f32_to_bf16(x * y)};
   else if constexpr (OP == OP_MIN) return (y < x) ? b : a;
-  else return (x < y) ? b : a;
+  else if constexpr (OP == OP_MAX) return (x < y) ? b : a;
 }
 
 // wrapping integer arithmetic (Go semantics) without signed-overflow UB
@@ -97,7 +116,10 @@ __device__ __forceinline__ T combine_any(T a, T b) {
 template <typename T, int OP>
 __device__ __forceinline__ pack_t combine16(pack_t a, pack_t b) {
   constexpr int N = 16 / sizeof(T);
-  if constexpr (__is_same(T, _Float16) && (OP == OP_SUM || OP == OP_PROD)) {
+  if constexpr (kBitOp<OP>) {
+    static_assert(kIntegerElem<T>, "a bitwise operator is never instantiated with a floating-point type or bf16_t (launch.h with_op)");
+    return bitop<OP>(a, b);  // the packet itself: v_and_b32 / v_or_b32 / v_xor_b32 x 4, no per-element loop
+  } else if constexpr (__is_same(T, _Float16) && (OP == OP_SUM || OP == OP_PROD)) {
     // packed halves: v_pk_add_f16 / v_pk_mul_f16, 2 elements per VALU lane-op
     union { pack_t u; half2_t h[4]; } x, y, r;
     x.u = a; y.u = b;
@@ -116,16 +138,21 @@ __device__ __forceinline__ pack_t combine16(pack_t a, pack_t b) {
 // 8-byte line (ll.hip: the payload of a {data, flag} line)
 template <typename T, int OP>
 __device__ __forceinline__ uint64_t combine8(uint64_t a, uint64_t b) {
-  constexpr int N = 8 / sizeof(T);
-  union {
-    uint64_t u;
-    T e[N];
-  } x, y, r;
-  x.u = a;
-  y.u = b;
+  if constexpr (kBitOp<OP>) {
+    static_assert(kIntegerElem<T>, "a bitwise operator is never instantiated with a floating-point type or bf16_t (launch.h with_op)");
+    return bitop<OP>(a, b);
+  } else {
+    constexpr int N = 8 / sizeof(T);
+    union {
+      uint64_t u;
+      T e[N];
+    } x, y, r;
+    x.u = a;
+    y.u = b;
 #pragma unroll
-  for (int i = 0; i < N; i++) r.e[i] = combine_any<T, OP>(x.e[i], y.e[i]);
-  return r.u;
+    for (int i = 0; i < N; i++) r.e[i] = combine_any<T, OP>(x.e[i], y.e[i]);
+    return r.u;
+  }
 }
 
 // ---- the accumulator of a fold: first source, N-1 times add(), result() ----------------------------------------------------

@@ -940,7 +940,7 @@ hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count,
   }
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_op<T>(op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
       if (aligned16(dst) && aligned16(a) && aligned16(b)) {
         const size_t npack = count / (16 / sizeof(T));
@@ -1036,7 +1036,7 @@ hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void*
         [&](int i, void* d, hipEvent_t e0, hipEvent_t e1) { return launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, e0, e1); });
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op(op, [&](auto o) {
+    return with_op<T>(op, [&](auto o) {
       const dim3 grid(batch_grid_x(maxc / (16 / sizeof(T)), n), n);
       return with_mode012(kernel_mode_for(3 * total * sizeof(T)), [&](auto m) {
         XMPI_LAUNCH((reduce2_batch_kernel<T, decltype(o)::value, decltype(m)::value>), grid, dim3(kBlock), s, es, ee, q);

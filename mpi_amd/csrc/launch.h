@@ -4,7 +4,7 @@
 //
 //   return with_dtype(dtype, [&](auto t) {
 //     using T = typename decltype(t)::type;
-//     return with_op(op, [&](auto o) {
+//     return with_op<T>(op, [&](auto o) {
 //       XMPI_LAUNCH((some_kernel<T, decltype(o)::value>), grid, dim3(kBlock), s, es, ee, args);
 //       return hipGetLastError();
 //     });
@@ -80,23 +80,34 @@ hipError_t with_dtype(int dtype, F&& f) {
   }
 }
 
-template <typename F>
+// The operators of every kernel that has one: the four arithmetic ones for every T, and the three bitwise ones for the integer
+// types -- for any other T they answer hipErrorInvalidValue and nothing is instantiated (kdev.h would refuse to compile it).
+template <typename T, typename F>
 hipError_t with_op(int op, F&& f) {
   switch (op) {
     case OP_SUM: return f(int_tag<OP_SUM>{});
     case OP_PROD: return f(int_tag<OP_PROD>{});
     case OP_MIN: return f(int_tag<OP_MIN>{});
     case OP_MAX: return f(int_tag<OP_MAX>{});
+    case OP_BAND:
+      if constexpr (kIntegerElem<T>) return f(int_tag<OP_BAND>{});
+      else return hipErrorInvalidValue;
+    case OP_BOR:
+      if constexpr (kIntegerElem<T>) return f(int_tag<OP_BOR>{});
+      else return hipErrorInvalidValue;
+    case OP_BXOR:
+      if constexpr (kIntegerElem<T>) return f(int_tag<OP_BXOR>{});
+      else return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }
 
 // The fold family's operators (kernels whose lane sees every contribution to an element: reduce_n*, dsync_fold, dsync_body, the LL
-// folds): the four of with_op and OP_SUM_WIDE -- handed through for the two 16-bit float types, OP_SUM for every other T, whose sum
+// folds): those of with_op and OP_SUM_WIDE -- handed through for the two 16-bit float types, OP_SUM for every other T, whose sum
 // it is.  A launcher of anything else (the stepped kernels, reduce2*) keeps to with_op and answers hipErrorInvalidValue.
 template <typename T, typename F>
 hipError_t with_fold_op(int op, F&& f) {
-  if (op != OP_SUM_WIDE) return with_op(op, f);
+  if (op != OP_SUM_WIDE) return with_op<T>(op, f);
   if constexpr (std::is_same_v<T, _Float16> || std::is_same_v<T, bf16_t>) return f(int_tag<OP_SUM_WIDE>{});
   else return f(int_tag<OP_SUM>{});
 }

@@ -36,6 +36,7 @@ int xmpi_reduce_local(xmpi_comm* c, void* dst, const void* a, const void* b, siz
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
   if (!es || op < 0 || op >= XMPI_OP_COUNT) return XMPI_ERR_ARG;
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   if (op == XMPI_SUM_WIDE) op = XMPI_SUM;  // two operands: the same bits (include/xmpi.h)
   struct Ctx { xmpi_comm* c; void* dst; const void *a, *b; size_t n; int dt, op; } ctx{c, dst, a, b, count, (int)dtype, (int)op};
   return timed_launch(c, PROF_REDUCE2, 3 * count * es,
@@ -51,6 +52,7 @@ int xmpi_reduce_local_n(xmpi_comm* c, void* dst, const void* const* srcs, int ns
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
   if (!es || op < 0 || op >= XMPI_OP_COUNT || nsrc < 1 || nsrc > kMaxReduceSrcs) return XMPI_ERR_ARG;
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   struct Ctx { xmpi_comm* c; void* dst; const void* const* s; int ns; size_t n; int dt, op; } ctx{c, dst, srcs, nsrc, count, (int)dtype, normal_op((int)dtype, (int)op)};
   return timed_launch(c, PROF_REDUCEN, (size_t)(nsrc + 1) * count * es,
                       [](void* p, hipEvent_t es, hipEvent_t ee) {
@@ -77,6 +79,7 @@ int xmpi_reduce_local_multi(xmpi_comm* c, void* const* dsts, int ndst, const voi
   const size_t es = xmpi_dtype_size(dtype);
   if (!es || op < 0 || op >= XMPI_OP_COUNT || nsrc < 1 || nsrc > kMaxReduceSrcs || ndst < 1 || ndst > kMaxReduceSrcs)
     return XMPI_ERR_ARG;
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   struct Ctx { xmpi_comm* c; void* const* d; int nd; const void* const* s; int ns; size_t n; int dt, op; }
       ctx{c, dsts, ndst, srcs, nsrc, count, (int)dtype, normal_op((int)dtype, (int)op)};
   return timed_launch(c, PROF_ZCOPY, (size_t)(nsrc + ndst) * count * es,
@@ -117,6 +120,7 @@ int xmpi_reduce_local_batch(xmpi_comm* c, void* const* dst, void* const* dst2, c
   XMPI_ENTER(c);
   const size_t es = xmpi_dtype_size(dtype);
   if (!es || op < 0 || op >= XMPI_OP_COUNT || n < 1 || n > kMaxBatch || !dst || !a || !b || !counts) return XMPI_ERR_ARG;
+  if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   if (op == XMPI_SUM_WIDE) op = XMPI_SUM;  // two operands per segment: the same bits (include/xmpi.h)
   size_t total = 0;
   for (int i = 0; i < n; i++) {

@@ -762,8 +762,9 @@ hipError_t launch_dsync_sched(const DsyncSchedArgs& a, int dtype, int op, int gr
   const dim3 grid((unsigned)grid_x, (unsigned)a.nchan);
   const bool moves_only = a.sched == SCHED_RING_ALLGATHER || a.sched == SCHED_TREE_BCAST;  // bytes, whatever the dtype: one kernel
   return with_dtype(moves_only ? (int)DT_U8 : dtype, [&](auto t) {
-    return with_op(moves_only ? (int)OP_SUM : op, [&](auto o) {
-      XMPI_LAUNCH((dsync_sched_kernel<typename decltype(t)::type, decltype(o)::value>), grid, dim3(kBlock), s, es, ee, a);
+    using T = typename decltype(t)::type;
+    return with_op<T>(moves_only ? (int)OP_SUM : op, [&](auto o) {
+      XMPI_LAUNCH((dsync_sched_kernel<T, decltype(o)::value>), grid, dim3(kBlock), s, es, ee, a);
       return hipGetLastError();
     });
   });

@@ -457,7 +457,11 @@ T fold1(T a, T b, xmpi_op op) {
 // XMPI_SUM_WIDE means XMPI_SUM here: it differs for the 16-bit float types only, which have no Go type and so none on this backend
 bool op_known(xmpi_op* op) {
   if (*op == XMPI_SUM_WIDE) *op = XMPI_SUM;
-  return *op == XMPI_SUM || *op == XMPI_PROD || *op == XMPI_MIN || *op == XMPI_MAX;
+  return *op == XMPI_SUM || *op == XMPI_PROD || *op == XMPI_MIN || *op == XMPI_MAX || *op == XMPI_BAND || *op == XMPI_BOR || *op == XMPI_BXOR;
+}
+// XMPI_BAND / _BOR / _BXOR are defined for the integer types (include/xmpi.h): decided before anything is exchanged
+bool bitwise_on_float(xmpi_op op, xmpi_dtype dt) {
+  return (op == XMPI_BAND || op == XMPI_BOR || op == XMPI_BXOR) && dt != XMPI_U8 && dt != XMPI_I32 && dt != XMPI_I64;
 }
 template <typename T>
 void fold_into(void* acc, const void* x, size_t n, xmpi_op op) {
@@ -473,6 +477,9 @@ void fold_into_int(void* acc, const void* x, size_t n, xmpi_op op) {
   for (size_t i = 0; i < n; i++) {
     if (op == XMPI_SUM) a[i] = (T)((U)a[i] + (U)b[i]);
     else if (op == XMPI_PROD) a[i] = (T)((U)a[i] * (U)b[i]);
+    else if (op == XMPI_BAND) a[i] = (T)((U)a[i] & (U)b[i]);
+    else if (op == XMPI_BOR) a[i] = (T)((U)a[i] | (U)b[i]);
+    else if (op == XMPI_BXOR) a[i] = (T)((U)a[i] ^ (U)b[i]);
     else a[i] = fold1<T>(a[i], b[i], op);
   }
 }
@@ -529,6 +536,7 @@ Error Network::Allgather(const Data& send, Data recv) {
 Error Network::Reduce(const Data& send, Data recv, xmpi_op op, int root) {
   if (root < 0 || root >= size_) return Error(XMPI_ERR_ARG, "mpi reduce: bad root");
   if (!op_known(&op)) return Error(XMPI_ERR_ARG, "mpi reduce: unknown operator");
+  if (bitwise_on_float(op, send.dtype)) return Error(XMPI_ERR_ARG, "mpi reduce: a bitwise operator needs an integer type");
   std::vector<std::vector<uint8_t>> all;
   if (Error e = exchange(send, &all, root)) return e;
   if (rank_ != root) return Error();
@@ -555,6 +563,7 @@ Error Network::Reduce(const Data& send, Data recv, xmpi_op op, int root) {
 Error Network::Allreduce(const Data& send, Data recv, xmpi_op op) {
   // every rank gathers everything and folds for itself -- what the oracle's definition says, not the cheapest schedule
   if (!op_known(&op)) return Error(XMPI_ERR_ARG, "mpi allreduce: unknown operator");
+  if (bitwise_on_float(op, send.dtype)) return Error(XMPI_ERR_ARG, "mpi allreduce: a bitwise operator needs an integer type");
   std::vector<std::vector<uint8_t>> all;
   if (Error e = exchange(send, &all, -1)) return e;
   const size_t es = elem_size(send.dtype), bytes = send.count * es;

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libxmpi.so")
 # enums of include/xmpi.h
 U8, I32, I64, F16, F32, F64, BF16 = range(7)
 SUM, PROD, MIN, MAX, SUM_WIDE = range(5)  # SUM_WIDE: f16 / bf16 accumulated in f32, rounded once (SUM for every other dtype)
+BAND, BOR, BXOR = 5, 6, 7  # bitwise AND / OR / XOR: U8, I32 and I64 only (a float dtype is XMPI_ERR_ARG)
 ALGO_AUTO, ALGO_RING, ALGO_RHD, ALGO_DIRECT, ALGO_TREE, ALGO_ZCOPY, ALGO_ZPUSH, ALGO_LL, ALGO_RING_PUSH, ALGO_RHD_PUSH, ALGO_TREE_PUSH = range(11)
 COLL_ALLREDUCE, COLL_ALLGATHER, COLL_BCAST, COLL_REDUCE, COLL_REDUCE_SCATTER, COLL_ALLTOALL = range(6)
 PAT_UNIFORM, PAT_INDEX, PAT_CONST, PAT_SIGNED = range(4)

@@ -34,6 +34,8 @@ int dsync_prepare(xmpi_comm* c) {
   // re-used: clearing is GPU work on a page seven other processes have mapped, and in a crowded GPU (eight ranks
   // plus a test runner with a context of its own) that one 64 KiB fill took 10-50 s.  Instead the epochs of the new
   // communicator start above everything an earlier one may have left in any rank's page (flag_epoch, dsync_connect).
+  // (All but the 12.5 KiB of the Send / Receive areas, whose records are ordered by numbers that start again with every
+  // communicator: one wave clears them in dsync_connect, in front of the flag self-test's kernel.)
   bool fresh = false;
   uint64_t last_epoch = 0;
   void* page = pool_acquire(c->device, kPageBytes, 1, &fresh, &last_epoch);
@@ -133,6 +135,20 @@ int dsync_connect(xmpi_comm* c, double timeout_s) {
     if (brc != XMPI_OK) {
       set_last_error("xmpi_init: a peer did not reach the flag self-test");
       return brc;
+    }
+  }
+  // The Send / Receive areas of this rank's page start out cleared (pool.cpp hands pages on as they were left): nothing in them is
+  // told from an earlier communicator's records by a number that would have to grow.  Behind the barrier above no peer of an
+  // earlier communicator writes here any more, and none of this one does before the vote below.  (XMPI_TEST_P2P_SEQ0 = S, tests:
+  // the areas as S messages per ordered pair, all consumed and answered, leave them.)
+  const uint64_t seq0 = (uint64_t)param_env("XMPI_TEST_P2P_SEQ0");
+  if (mapped) {
+    hipError_t e = launch_p2p_reset(c->dpage, seq0, c->local_stream);
+    if (e == hipSuccess && !c->dsync_status_dev) e = hipStreamSynchronize(c->local_stream);  // (else: with the self-test behind it)
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (!me->maps_why[0]) snprintf(me->maps_why, sizeof me->maps_why, "rank %d: clearing the Send / Receive boxes: %s", c->rank, hipGetErrorString(e));
+      mapped = false;
     }
   }
   if (mapped && c->dsync_status_dev) {
@@ -258,8 +274,10 @@ int dsync_connect(xmpi_comm* c, double timeout_s) {
   if (c->body_sys < 0) c->body_sys = 0;
   // epochs of this communicator: above whatever earlier communicators left in ANY rank's (pooled, uncleared) page;
   // the same number on every rank.  It also tags the translations this communicator's kernels cache in the page.
-  uint64_t base = 0;
+  // (XMPI_TEST_EPOCH_BASE, tests: ... or above that many, as if the pages had seen them -- the counters' 32-bit edges in minutes)
+  uint64_t base = (uint64_t)param_env("XMPI_TEST_EPOCH_BASE");
   for (int p = 0; p < N; p++) base = std::max(base, c->ctl->info(p)->flag_epoch);
+  for (int p = 0; p < N; p++) c->p2p_out_seq[p] = seq0;
   c->dsync_epoch = base;
   c->dsync_base = base;
   c->dsync_tag = base + 1;

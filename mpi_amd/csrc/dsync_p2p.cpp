@@ -111,7 +111,7 @@ int dsync_send(xmpi_comm* c, const void* buf, size_t bytes, int dtype, int dest,
   }
   P2PArgs a;
   p2p_fill(c, &a, dest, tag, dtype);
-  a.seq = ((c->dsync_tag & 0xffffffffull) << 32) | (c->p2p_out_seq[dest] + 1);  // (consumed below, once the kernel is enqueued)
+  a.seq = c->p2p_out_seq[dest] + 1;  // all 64 bits, and nothing else in the word (consumed below, once the kernel is enqueued)
   a.bytes = bytes;
   a.gen = ref.gen;
   a.slot = (uint64_t)slot;
@@ -137,9 +137,8 @@ int dsync_recv(xmpi_comm* c, void* buf, size_t cap_bytes, int dtype, int src, in
   p2p_fill(c, &a, src, tag, dtype);
   a.bytes = cap_bytes;
   a.buf = buf;
-  // unique per PAGE, not per communicator: the page is pooled and never cleared, a later communicator's first receive must
-  // not match the go record an earlier one left behind (the communicator number is what a.seq carries as well)
-  a.op_id = ((c->dsync_tag & 0xffffffffull) << 32) | (++c->p2p_op_id & 0xffffffffull);
+  // unique per communicator, never 0: the go records of the (pooled) page were cleared when this communicator connected
+  a.op_id = ++c->p2p_op_id;
   const int ds = p2p_done_slot(c, &a);
   // a few blocks for a large message; every block but the first only waits for the first (a local word)
   long gx = (long)((cap_bytes + 16383) >> 14);

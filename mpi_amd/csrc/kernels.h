@@ -126,7 +126,7 @@ constexpr size_t kStepOff = 65536;
 constexpr int kP2PBoxes = 8;  // messages in flight per ordered rank pair (stream-ordered Send / Receive)
 constexpr size_t kBoxOff = kStepOff + sizeof(uint64_t) * kDsyncRanks * kStepSlots;
 struct P2PBox {
-  uint64_t seq;    // written last (release): message number of the ordered pair, 1-based; box = (seq - 1) % kP2PBoxes
+  uint64_t seq;    // written last (release): message number of the ordered pair, 1-based, 64 bits; box = (seq - 1) % kP2PBoxes
   uint64_t tag;    // low 32 bits: the tag (as int32), bits 32..39: dtype
   uint64_t bytes;
   uint64_t gen, slot, off;  // where the payload lives: the sender's registration number, table slot, byte offset
@@ -185,14 +185,24 @@ static_assert(kVBoxOff + sizeof(VBox) * kDsyncRanks <= kLLHereOff, "flag allocat
 // at least one line to EVERY peer and collects one from every peer before it completes -- "a rank completes only after every peer
 // has started" holds by the data alone, without the `here` words.  A slot holds one source's payload, and each source sends this
 // rank exactly one block: the limit is kLLMaxPayload per BLOCK.
+// Counters and their widths.  The epoch is 64 bits (DsyncPage::epoch_now, counted by the kernels), a line's flag its low 32 bits with 0
+// written as 1 (a cleared line never matches).  Flags are compared for EQUALITY, never ordered, and consecutive epochs use slots of
+// different parity, so epochs k 2^32 and k 2^32 + 1 -- both flag 1 -- are told apart by where they lie, and a communicator whose
+// flags are smaller than its predecessor's (born past a multiple of 2^32) reads nothing stale.  The stated limit of a 32-bit flag: a
+// line written exactly 2^32 epochs (or a multiple) earlier, at the same parity, and never rewritten since, carries a matching flag.
+// A slot is rewritten by every LL collective of its parity, so that takes a job whose pages lay untouched by LL lines for 2^32
+// epochs -- hours at the least -- and then sends its first line of that epoch's parity; it is not guarded against.
+// The step words of the stepped kernels are (epoch << 8) | step in 64 bits, compared for order: sound below epoch 2^56.
+// tests/epoch_scenarios.py runs every form across epochs 2^31, 2^32, 3 * 2^32 and 2^40 (XMPI_TEST_EPOCH_BASE).
 constexpr size_t kLLOff = 1u << 20;
 constexpr size_t kLLSlotBytes = 64u << 10;          // lines of one (source rank, parity)
 constexpr size_t kLLMaxPayload = kLLSlotBytes / 2;  // 32 KiB per rank
 static_assert(kLLHereOff + 64 * kDsyncRanks <= kLLOff, "flag allocation");
 // The v-boxes (VBox above) are single-buffered, and rank p may rewrite vbox[p] of rank q's allocation at its next xmpi_alltoallv:
 // a call completes on p only after q said "done" (kdev.h dsync_end), and every block of q read the box before it took the ticket
-// q's "done" waits for.  A box is matched by the collective's epoch, which only grows, and a communicator's epochs start above
-// what earlier users of the pooled pages left (DsyncArgs::epoch_floor): the pages need no clearing for the boxes either.
+// q's "done" waits for.  A box is matched by the collective's epoch (all 64 bits, compared for equality), which only grows, and a
+// communicator's epochs start above what earlier users of the pooled pages left (DsyncArgs::epoch_floor): the pages need no clearing
+// for the v-boxes or the announce slots (DsyncSlot::epoch, matched the same way).  The Send / Receive areas ARE cleared at connect.
 static_assert(kLLOff + kLLSlotBytes * 2 * kDsyncRanks <= kDsyncPageBytes, "flag allocation");
 
 // what a block of the kernel moves: the fold of the source ranks' buffers (rank order) -> the destination ranks'
@@ -388,6 +398,11 @@ hipError_t launch_sys_copy(void* dst, const void* src, size_t bytes, int grid_x,
 // flag allocation and waits for the receiver's ack; the receiver's kernel waits for a box with its tag, pulls the payload
 // straight out of the sender's buffer and acks with its verdict.  What the reference does with a gob message and an ack
 // message over a net.Conn (network.go:562-571, 616-624).
+// seq is the ordered pair's message number, 1-based, in all 64 bits of the word; acks and `taken` words hold such numbers and are
+// compared for ORDER (ack >= seq, seq > taken).  That is sound because a communicator's numbers only grow and because it starts from
+// cleared boxes, acks, `taken` words and go records: the pages are pooled, and dsync_connect clears these areas of its own page
+// (launch_p2p_reset) between its barriers.  (They used to be told from an earlier communicator's by its number in the upper 32
+// bits, which stopped growing at 2^32 epochs, and the message number carried into it at 2^32 messages.)
 struct P2PArgs {
   DsyncPage* my_page;    // this rank's flag allocation
   DsyncPage* peer_page;  // the other rank's, as mapped here
@@ -403,10 +418,13 @@ struct P2PArgs {
   uint64_t spin_limit;
   uint64_t* host_done;   // pinned host: [0] = done flag (written last), [1] = status, [2] = bytes received; may be null
   uint64_t done_value;   // what to write into host_done[0]
-  uint64_t op_id;        // receive: (communicator number << 32) | number of this operation -- unique per PAGE, which outlives
-                         // communicators and is never cleared; go slot = op_id % kP2PGoSlots
+  uint64_t op_id;        // receive: number of this operation of the communicator, from 1 (the go records of the pooled page are
+                         // cleared at connect); go slot = op_id % kP2PGoSlots
 };
 hipError_t launch_p2p_send(const P2PArgs& a, hipStream_t stream);
+// The boxes, acks, `taken` words and go records of `page` (this rank's own allocation) as after seq0 messages of every ordered pair,
+// all consumed and answered; seq0 = 0 clears them.  One wave; dsync_connect runs it between its barriers.
+hipError_t launch_p2p_reset(DsyncPage* page, uint64_t seq0, hipStream_t stream);
 // the copy of a blocking Receive the host has already matched: dst = src, then the acks (see sched.hip)
 struct P2PPullArgs {
   void* dst;

@@ -125,6 +125,10 @@ const Param kParams[] = {
     {nullptr, "XMPI_P2P_DEPTH", nullptr, nullptr, 2, 2, 16, 0},
     {"p2p_slot_bytes", "XMPI_P2P_SLOT_BYTES", nullptr, READ(c->p2p_slot_bytes), 4l << 20, 4096, kAny, 0},
     {nullptr, "XMPI_HOST_LANES", nullptr, nullptr, 1, 0, 1, B},  // a request: the creator of the block sizes and reserves them
+    // tests only (read by dsync_connect, the same on every rank; no name: nothing sets or reads them back): where the communicator's
+    // epochs start at least, and how many Send / Receive messages every ordered pair counts as having exchanged already
+    {nullptr, "XMPI_TEST_EPOCH_BASE", nullptr, nullptr, 0, 0, kAny, 0},
+    {nullptr, "XMPI_TEST_P2P_SEQ0", nullptr, nullptr, 0, 0, kAny, 0},
     // process-wide: their own pair normalises what it is given (a mode outside 0 .. 2 is -1, a negative cap 0)
     {"kernel_mode", "XMPI_KERNEL_MODE", nullptr, READ(get_kernel_mode()), -1, -1, 2, W, set_kernel_mode},
     {"grid_cap", "XMPI_GRID_CAP", nullptr, READ(get_grid_cap()), 0, 0, INT_MAX, W, set_grid_cap},

@@ -401,18 +401,44 @@ __device__ __forceinline__ void p2p_host_done(const P2PArgs& a, uint64_t status,
   __hip_atomic_store(a.host_done, a.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// One wave on the owner's GPU, inside xmpi_init (dsync_connect, between its two barriers: no peer of this communicator has written
+// here yet, the peers of an earlier one have finished): the Send / Receive areas of this rank's (pooled) flag allocation as a
+// communicator leaves them whose every ordered pair has exchanged seq0 messages, all consumed and answered -- seq0 = 0: cleared.
+// Lane p * kP2PBoxes + b has box b of rank p, the ack and the `taken` word that go with it, and one go record.
+__global__ __launch_bounds__(64) void p2p_reset_kernel(DsyncPage* page, uint64_t seq0) {
+  static_assert(kDsyncRanks * kP2PBoxes == 64 && kP2PGoSlots == 64, "one lane per box, per ack, per go record");
+  static_assert(sizeof(P2PBox) == 64 && sizeof(P2PAck) == 64 && sizeof(P2PGo) == 64, "records of eight words");
+  const int t = threadIdx.x;
+  // the last message of the pair that went through box b: the largest n <= seq0 with (n - 1) % kP2PBoxes == b
+  const uint64_t b = (uint64_t)(t % kP2PBoxes);
+  const uint64_t last = seq0 > b ? seq0 - (seq0 - 1 - b) % kP2PBoxes : 0;
+  uint64_t* box = reinterpret_cast<uint64_t*>(p2p_boxes(page) + t);
+  uint64_t* ack = reinterpret_cast<uint64_t*>(p2p_acks(page) + t);
+  uint64_t* go = reinterpret_cast<uint64_t*>(p2p_go(page) + t);
+  for (int w = 1; w < 8; w++) {
+    st_sys64(box + w, 0);
+    st_sys64(ack + w, 0);
+    st_sys64(go + w, 0);
+  }
+  st_sys64(go, 0);
+  st_sys64(p2p_taken(page) + t, last);
+  st_sys64(box, last);  // (P2PBox::seq, P2PAck::seq: word 0)
+  st_sys64(ack, last);
+}
+
 // One wave.  Message `seq` of the pair goes into box (seq - 1) % kP2PBoxes of the receiver's allocation -- once the
 // message that used the box before has been answered -- and the kernel ends when the receiver has answered this one:
 // the payload has been consumed, the caller's buffer is free (the rendezvous of network.go:569).
 __global__ __launch_bounds__(64) void p2p_send_kernel(P2PArgs a) {
   if (threadIdx.x != 0) return;
-  // a.seq = (communicator number << 32) | n: pages are pooled and never cleared, the communicator number keeps the
-  // message numbers of successive communicators apart (and growing)
-  const uint64_t n = a.seq & 0xffffffffull;
+  // a.seq = n, the pair's message number in all 64 bits (no job sends 2^64 messages): the numbers of a communicator only grow, and
+  // those of an earlier communicator are gone -- the boxes, acks and `taken` words of a pooled page are cleared at connect
+  // (p2p_reset_kernel).  Nothing is packed beside n, so no carry out of its low 32 bits can reach anything else.
+  const uint64_t n = a.seq;
   const int b = (int)((n - 1) % kP2PBoxes);
   P2PAck* ack = p2p_acks(a.my_page) + (size_t)a.peer * kP2PBoxes + b;  // written by the receiver
   uint32_t why = DSYNC_OK;
-  if (n > (uint64_t)kP2PBoxes) why = p2p_spin(&ack->seq, a.seq - kP2PBoxes, a);
+  if (n > (uint64_t)kP2PBoxes) why = p2p_spin(&ack->seq, n - kP2PBoxes, a);
   uint64_t status = 0;
   if (why == DSYNC_OK) {
     P2PBox* box = p2p_boxes(a.peer_page) + (size_t)a.me * kP2PBoxes + b;
@@ -457,7 +483,7 @@ __global__ __launch_bounds__(kBlock) void p2p_recv_kernel(P2PArgs a) {
         for (int b = 0; b < kP2PBoxes; b++) {  // the oldest unconsumed message with this tag
           const uint64_t s = __hip_atomic_load(&boxes[b].seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
           const uint64_t tk = ld_sys64(&taken[b]);
-          if ((s >> 32) != (a.comm_tag & 0xffffffffull) || s <= tk || s >= best) continue;  // not this communicator's / consumed
+          if (s <= tk || s >= best) continue;  // empty (0: cleared at connect) / consumed
           if ((int32_t)(uint32_t)ld_sys64(&boxes[b].tag) != a.tag) continue;
           best = s;
           best_taken = tk;
@@ -745,6 +771,12 @@ hipError_t launch_flag_selftest(DsyncPage* const* page, int me, int n, uint64_t 
   a.abort_word = abort_word;
   a.seen = seen_out;
   hipLaunchKernelGGL(flag_selftest_kernel, dim3(1), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_p2p_reset(DsyncPage* page, uint64_t seq0, hipStream_t s) {
+  if (!page) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(p2p_reset_kernel, dim3(1), dim3(64), 0, s, page, seq0);
   return hipGetLastError();
 }
 

@@ -13,22 +13,37 @@ one at a time, in order).  What it checks is what the header claims:
   I4  pages are pooled and never cleared: a later communicator (epochs above everything its pages have seen) is not
       confused by stale lines.
 
+The flag of a line has the kernels' width: the low 32 bits of the epoch, 0 written as 1 (a cleared page never matches), the slot's
+parity from the full epoch -- epochs k 2^32 and k 2^32 + 1 carry the same flag 1 in different slots.  `epoch_base` starts the first
+communicator next to such an edge (XMPI_TEST_EPOCH_BASE).  Stated limit, not modelled: a line left exactly 2^32 epochs earlier at the
+same parity and never rewritten since carries a matching flag (kernels.h).
+
 `bugs` switches known-bad variants on so the tests can show the checker notices them: "no_here" (broadcast / reduce
-without the `here` words), "one_slot" (no parity), "flag_on_first_half_only", "no_epoch_base".
+without the `here` words), "one_slot" (no parity), "flag_on_first_half_only", "no_epoch_base", "zero_flag" (epoch k 2^32 written as
+flag 0: what a cleared line already says).
 """
 from __future__ import annotations
 
 import random
 
 
+M32 = (1 << 32) - 1
+
+
 class Violation(AssertionError):
     pass
 
 
+def flag_of(epoch, bugs=()):
+    """ll.hip: flag = (uint32_t)epoch ? (uint32_t)epoch : 1u"""
+    f = epoch & M32
+    return f if f or "zero_flag" in bugs else 1
+
+
 class Page:
     def __init__(self, n, lines):
-        # slot[src][parity][line][half] = (flag epoch, payload tag)
-        self.slot = [[[[(0, None), (0, None)] for _ in range(lines)] for _ in range(2)] for _ in range(n)]
+        # slot[src][parity][line][half] = (flag, payload tag, the epoch it was written for -- the checker's own note, not in the line)
+        self.slot = [[[[(0, None, 0), (0, None, 0)] for _ in range(lines)] for _ in range(2)] for _ in range(n)]
         self.here = [0] * n
         self.ready = [0] * n
         self.done = [0] * n
@@ -59,14 +74,14 @@ class Kernel:
         self.uses_here = kind in ("bc", "rd")
 
 
-def run(n, lines, program, seed, comms=1, bugs=()):
+def run(n, lines, program, seed, comms=1, bugs=(), epoch_base=0):
     """program: list of (kind, root) every rank runs per communicator.  Raises Violation; returns the scheduler steps."""
     rng = random.Random(seed)
     pages = [Page(n, lines) for _ in range(n)]
     last_epoch = [0] * n
     steps = 0
     for comm in range(comms):
-        base = max(last_epoch) if "no_epoch_base" not in bugs else 0
+        base = max(max(last_epoch), epoch_base) if "no_epoch_base" not in bugs else 0
         queue = [[Kernel(r, base + 1 + k, kind, root, n, lines) for k, (kind, root) in enumerate(program)] for r in range(n)]
         cur = [0] * n
         kernels = {(r, k.epoch): k for r in range(n) for k in queue[r]}
@@ -107,17 +122,17 @@ def run(n, lines, program, seed, comms=1, bugs=()):
                     ln = k.lanes[i]
                     if ln.todo:  # one 8-byte store into a peer's page
                         p, h = ln.todo.pop(rng.randrange(len(ln.todo)) if rng.random() < 0.3 else 0)
-                        old_e, _ = pages[p].slot[r][par][i][h]
+                        _, _, old_e = pages[p].slot[r][par][i][h]
                         victim = kernels.get((p, old_e))  # the kernel of rank p this half was written for
                         if victim is not None and old_e != e and not victim.ended and victim.lanes and (r, h) in victim.lanes[i].need:
                             raise Violation(f"I1: rank {r} (epoch {e}) overwrites line {i}.{h} that rank {p}'s epoch {old_e} has not read")
-                        pages[p].slot[r][par][i][h] = (e, (r, e, i, h))
+                        pages[p].slot[r][par][i][h] = (flag_of(e, bugs), (r, e, i, h), e)
                     else:  # one 8-byte load from my own page
                         p, h = rng.choice(sorted(ln.need))
-                        f, tag = mine.slot[p][par][i][h]
-                        trust = f == e
+                        f, tag, _ = mine.slot[p][par][i][h]
+                        trust = f == flag_of(e, bugs)
                         if "flag_on_first_half_only" in bugs and h == 1:  # the reader trusts the first half's flag for both
-                            trust = mine.slot[p][par][i][0][0] == e
+                            trust = mine.slot[p][par][i][0][0] == flag_of(e, bugs)
                         if trust:
                             if tag != (p, e, i, h):
                                 raise Violation(f"I2: rank {r} epoch {e} accepted {tag} as rank {p}'s line {i}.{h}")

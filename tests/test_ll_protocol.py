@@ -48,3 +48,34 @@ def test_known_bad_variants_are_caught(bug, program):
         except ll_sim.Violation:
             caught += 1
     assert caught > 0, f"the checker does not notice '{bug}'"
+
+
+EDGES = [(1 << 31), (1 << 32), 3 << 32, 1 << 40]
+
+
+@pytest.mark.parametrize("edge", EDGES)
+@pytest.mark.parametrize("n", [2, 3, 8])
+def test_the_mixed_program_across_a_32_bit_edge(n, edge):
+    """the first communicator born 5 epochs below the edge (the flag is the low 32 bits of the epoch, 0 written as 1; epochs k 2^32 and
+    k 2^32 + 1 carry the same flag in slots of different parity), its successor on the same pages above it"""
+    for seed in range(6):
+        ll_sim.run(n, lines=2, program=MIXED, seed=seed, comms=2, epoch_base=edge - 5)
+        ll_sim.run(n, lines=2, program=[("ar", 0)] * 8, seed=seed, comms=1, epoch_base=edge - 1)  # (the first epoch is the edge itself)
+
+
+def test_succession_across_2_to_the_32():
+    """A runs from 2^32 - 40 to 2^32 - 24 and stops; B, C, D follow on the same pages, each above what the one before left: the flags
+    of B's lines are SMALLER than those A left -- nothing in the LL protocol orders flags, it compares them for equality"""
+    for n, seed in itertools.product([2, 3], range(8)):
+        ll_sim.run(n, lines=2, program=MIXED, seed=seed, comms=4, epoch_base=(1 << 32) - 40)
+
+
+def test_a_zero_flag_at_the_edge_is_caught():
+    """epoch 2^32 written as flag 0 is what a cleared line says already: the checker notices (it is why the kernels write 1)"""
+    caught = 0
+    for seed in range(30):
+        try:
+            ll_sim.run(3, lines=2, program=[("ar", 0)] * 6, seed=seed, epoch_base=(1 << 32) - 1, bugs=("zero_flag",))  # (the first epoch, on lines nobody has written)
+        except ll_sim.Violation:
+            caught += 1
+    assert caught > 0, "the checker does not notice a flag of 0"

@@ -48,18 +48,77 @@ def test_a_stream_that_waits_for_work_behind_it_deadlocks():
 
 
 def test_records_of_an_earlier_communicator_are_not_matched():
-    """pages are pooled and never cleared: a box may still hold a message of the communicator before, even one that was
-    never consumed (its job was aborted) -- the communicator number in the message number keeps it out"""
-    stale = {(0, 1): [((1 << 32) | (b + 1), 5) for b in range(sim.K)]}  # communicator 1 left 8 messages with tag 5
+    """pages are pooled: a box may still hold a message of the communicator before, even one that was never consumed (its job was
+    aborted) -- the next communicator clears the boxes of its page when it connects"""
+    stale = {(0, 1): [(b + 1, 5) for b in range(sim.K)]}  # the communicator before left 8 messages with tag 5
     for seed in range(10):
         ops = {0: [[("send", 1, 5, "fresh")]], 1: [[("recv", 0, 5)]]}
         got = sim.run(ops, seed=seed, comm_tag=2, stale=stale, bugs=("stale_unconsumed",))
         assert got[(1, 0, 0)] == "fresh"
-    with pytest.raises(AssertionError):  # ... and the checker notices when the communicator number is not looked at
+    with pytest.raises(AssertionError):  # ... and the checker notices when it does not
         for seed in range(10):
             got = sim.run({0: [[("send", 1, 5, "fresh")]], 1: [[("recv", 0, 5)]]}, seed=seed, comm_tag=2, stale=stale,
-                          bugs=("stale_unconsumed", "no_comm_check"))
+                          bugs=("stale_unconsumed", "no_clear"))
             assert got[(1, 0, 0)] == "fresh"
+    # the protocol before (nothing cleared, the communicator's number in the upper half of the word) kept such a record out by that
+    # number -- and the checker notices when it is not looked at
+    stale = {(0, 1): [((1 << 32) | (b + 1), 5) for b in range(sim.K)]}
+    for seed in range(10):
+        got = sim.run({0: [[("send", 1, 5, "fresh")]], 1: [[("recv", 0, 5)]]}, seed=seed, comm_tag=2, stale=stale, bugs=("stale_unconsumed",), protocol="packed")
+        assert got[(1, 0, 0)] == "fresh"
+    with pytest.raises(AssertionError):
+        for seed in range(10):
+            got = sim.run({0: [[("send", 1, 5, "fresh")]], 1: [[("recv", 0, 5)]]}, seed=seed, comm_tag=2, stale=stale,
+                          bugs=("stale_unconsumed", "no_comm_check"), protocol="packed")
+            assert got[(1, 0, 0)] == "fresh"
+
+
+def _ping(m):
+    """m messages 0 -> 1 and their echoes, tags alternating"""
+    return {0: [[("send", 1, 40 + (k & 1), f"m{k}") for k in range(m)] + [("recv", 1, 40 + (k & 1)) for k in range(m)]],
+            1: [[("recv", 0, 40 + (k & 1)) for k in range(m)] + [("send", 0, 40 + (k & 1), f"e{k}") for k in range(m)]]}
+
+
+def _check_ping(got, m):
+    assert [got[(1, 0, k)] for k in range(m)] == [f"m{k}" for k in range(m)] and [got[(0, 0, m + k)] for k in range(m)] == [f"e{k}" for k in range(m)]
+
+
+A_TAG, B_TAG = (1 << 32) - 40 + 1, (1 << 32) + 60 + 1  # born at epoch 2^32 - 40; its successor, born at 2^32 + 60
+
+
+def _left_by(tag32, packed):
+    """what a communicator that exchanged 11 messages per pair, all consumed and answered, leaves in every box"""
+    last = [11 - (11 - 1 - b) % sim.K for b in range(sim.K)]
+    return {pair: [(((tag32 << 32) | n) if packed else n, 41) for n in last] for pair in ((0, 1), (1, 0))}
+
+
+def test_a_communicator_that_succeeds_one_across_2_to_the_32():
+    """B's number is smaller than A's in its low 32 bits.  Before, that left every `taken` word above every message B would ever post (a
+    receive that never matches) and every ack above everything B's sends wait for (a send that completes unconsumed): the model reports
+    it at those semantics, and nothing with the pages cleared at connect"""
+    for seed in range(10):
+        _check_ping(sim.run(_ping(12), seed=seed, comm_tag=B_TAG, stale=_left_by(A_TAG & sim.M32, False)), 12)
+    seen = set()
+    for seed in range(10):
+        with pytest.raises(sim.Violation) as e:
+            sim.run(_ping(12), seed=seed, comm_tag=B_TAG, stale=_left_by(A_TAG & sim.M32, True), protocol="packed")
+        seen.add("deadlock" if "deadlock" in str(e.value) else "early" if "completed before" in str(e.value) else str(e.value))
+    assert seen <= {"deadlock", "early"} and "early" in seen, seen  # (the silent one: a Send that says "consumed" to nobody)
+    # the other way round -- numbers that grow -- the old protocol was right: the model does not cry wolf
+    for seed in range(10):
+        _check_ping(sim.run(_ping(12), seed=seed, comm_tag=B_TAG + 100, stale=_left_by(B_TAG & sim.M32, True), protocol="packed"), 12)
+
+
+def test_message_2_to_the_32_of_a_pair():
+    """40 messages from message 2^32 - 15 on.  Before, message 2^32 carried into the communicator's number and its n read 0 -- box 7,
+    no wait for the box's ack: reported at those semantics; the 64-bit number passes"""
+    s0 = (1 << 32) - 16
+    for seed in range(10):
+        _check_ping(sim.run(_ping(40), seed=seed, comm_tag=7, seq0=s0), 40)
+        with pytest.raises(sim.Violation):
+            sim.run(_ping(40), seed=seed, comm_tag=7, seq0=s0, protocol="packed")
+    for seed in range(5):  # (far from the edge the old protocol passes with the same seeding)
+        _check_ping(sim.run(_ping(40), seed=seed, comm_tag=7, seq0=800, protocol="packed"), 40)
 
 
 def test_the_checker_notices_a_missing_box_wait():

@@ -24,7 +24,8 @@ ENV_VARS = ["XMPI_TIMEOUT_S", "XMPI_WATCHDOG_MS", "XMPI_SELFCHECK", "XMPI_ZERO_C
             "XMPI_P2P_GRID_CAP", "XMPI_DSYNC_SPLIT_BYTES", "XMPI_DSYNC_UNROLL", "XMPI_DSYNC_TILES", "XMPI_DSYNC_GRID", "XMPI_SCHED_CHANNELS",
             "XMPI_SCHED_GRID", "XMPI_TREE_PIECE_BYTES", "XMPI_ZC_BCAST_PUSH_BYTES", "XMPI_BODY_SYS", "XMPI_XCD_CHECK", "XMPI_CHANNELS",
             "XMPI_PIECE_BYTES", "XMPI_COPY_ENGINE", "XMPI_BATCH_COPIES", "XMPI_ONESHOT_BYTES", "XMPI_ZC_GROUP_LAUNCH", "XMPI_SHARED_STREAM",
-            "XMPI_LANES", "XMPI_FIFO_DEPTH", "XMPI_SLOT_BYTES", "XMPI_P2P_DEPTH", "XMPI_P2P_SLOT_BYTES", "XMPI_KERNEL_MODE", "XMPI_GRID_CAP"]
+            "XMPI_LANES", "XMPI_FIFO_DEPTH", "XMPI_SLOT_BYTES", "XMPI_P2P_DEPTH", "XMPI_P2P_SLOT_BYTES", "XMPI_KERNEL_MODE", "XMPI_GRID_CAP",
+            "XMPI_TEST_EPOCH_BASE", "XMPI_TEST_P2P_SEQ0"]  # (tests only; one rank never meets on the device: nothing to see)
 
 # ---- what may differ from the parent, and why ---------------------------------------------------------------------------------------
 # xmpi_get_param answered -1 for these on the parent (they could only be set); they are rows like any other now

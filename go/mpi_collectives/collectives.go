@@ -32,6 +32,7 @@ type Personal interface {
 
 // The reduction operators a Collective / Personal backend takes as `op`: the values of xmpi_op (include/xmpi.h), which
 // xgmi.Sum ... xgmi.BXor share.  OpBAnd / OpBOr / OpBXor are bitwise and defined for integer element types only.
+// OpSumWide accumulates xgmi.F16 / BF16 / F8E4M3 / F8E5M2 in f32 and rounds once; for every other element type it is OpSum.
 const (
 	OpSum = iota
 	OpProd

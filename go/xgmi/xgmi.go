@@ -54,6 +54,11 @@ const (
 	F32
 	F64
 	BF16
+	// F8E4M3, F8E5M2: the OCP 8-bit floats (one byte per element; Go has no such type: a DeviceBuffer of them is filled from
+	// raw bytes).  Moved like U8 by everything without an operator; reduced -- every operator, SumWide included, which is not
+	// rewritten to Sum for them -- by the schedules in which one lane sees every contribution (ring, halving and tree refuse).
+	F8E4M3
+	F8E5M2
 )
 
 // Op mirrors xmpi_op.

@@ -30,7 +30,17 @@ extern "C" {
 typedef struct xmpi_comm xmpi_comm;
 
 /* element types (the reference types payloads by Go reflection through gob,
- * network.go:539,597; a device buffer needs an explicit tag) */
+ * network.go:539,597; a device buffer needs an explicit tag)
+ * XMPI_F8E4M3 / XMPI_F8E5M2 are the OCP 8-bit floating-point formats (v1.0; torch.float8_e4m3fn / float8_e5m2), one byte each:
+ *   E4M3  S.EEEE.MMM, bias 7, no infinities, S.1111.111 (0x7F, 0xFF) is NaN, largest finite 448 (0x7E), smallest subnormal 2^-9
+ *   E5M2  S.EEEEE.MM, bias 15, IEEE-like: 0x7C / 0xFC +-inf, 0x7D..0x7F / 0xFD..0xFF NaN, largest finite 57344 (0x7B), smallest
+ *         subnormal 2^-16
+ * Their arithmetic is defined in software and the hardware conversions are held to it: f32(x) is exact; narrow(f) gives a NaN of the
+ * type for a NaN (which one is unspecified), +-inf for +-inf (E5M2), and otherwise rounds to nearest, ties to even, with gradual
+ * underflow, and SATURATES: a rounded magnitude above the largest finite one becomes +-448 / +-57344 (the default of HIP's __hip_fp8
+ * types), so a sum of finite inputs never turns into inf or NaN.  Everything without an operator (bcast, allgather, all-to-all,
+ * alltoallv, Send / Receive, xmpi_copy_local*) moves them as any one-byte element, by every schedule name; a rank passing E4M3 is
+ * not in the same call as a rank passing E5M2 or U8.  Their reductions: see xmpi_op. */
 typedef enum {
   XMPI_U8 = 0,
   XMPI_I32 = 1,
@@ -39,7 +49,9 @@ typedef enum {
   XMPI_F32 = 4,
   XMPI_F64 = 5,
   XMPI_BF16 = 6,
-  XMPI_DTYPE_COUNT = 7,
+  XMPI_F8E4M3 = 7,
+  XMPI_F8E5M2 = 8,
+  XMPI_DTYPE_COUNT = 9,
   /* (every int is a value of the type: what a binding passes out of range -- cgo hands over a uint32 -- comes back as
    * XMPI_ERR_ARG instead of being undefined behaviour in the C++ that reads it; the same for the two enums below) */
   XMPI_DTYPE_ANY_INT = 0x7fffffff
@@ -67,7 +79,16 @@ typedef enum {
  * unregistered memory, xmpi_reduce_local and its _n / _multi / _batch forms; routing is by size as for XMPI_MAX.  With XMPI_F16 / F32 /
  * F64 / BF16 the call is XMPI_ERR_ARG on every rank, from the arguments alone, before anything is announced or launched: the
  * communicator stays usable and xmpi_last_error says that a bitwise operator needs an integer type.  Ranks passing different ones
- * are not in the same call (XMPI_ERR_ARG on every rank), like any two operators. */
+ * are not in the same call (XMPI_ERR_ARG on every rank), like any two operators.
+ * XMPI_F8E4M3 / XMPI_F8E5M2: XMPI_SUM and XMPI_PROD fold in rank order and narrow after every contribution, acc = narrow(f32(acc) op
+ * f32(x_r)); XMPI_MIN / XMPI_MAX compare the widened values and return the chosen operand's own byte; XMPI_SUM_WIDE is NOT rewritten
+ * to XMPI_SUM: for N >= 2 it is narrow(((f32(x0) + f32(x1)) + f32(x2)) + ...), IEEE f32 additions in rank order, narrowed once (with
+ * two contributions the same bits as XMPI_SUM); one contribution is copied unchanged; the bitwise operators are XMPI_ERR_ARG as for
+ * the other float types.  All five run where XMPI_SUM_WIDE runs, and there only -- AUTO, ZCOPY, ZPUSH, LL, DIRECT, the stream-ordered,
+ * captured, non-blocking and _repeat forms, host slices and unregistered memory, every layout of the ranks, xmpi_reduce_scatter,
+ * xmpi_reduce_local and its _n / _multi / _batch forms.  RING, RHD, TREE and their PUSH forms named by the caller for a reduction of
+ * these types answer XMPI_ERR_UNSUPPORTED on every rank, before anything is announced (partial sums of two or three mantissa bits
+ * passed round a ring are not offered); AUTO whose tuned table names one of them runs the fold. */
 typedef enum {
   XMPI_SUM = 0,
   XMPI_PROD = 1,
@@ -461,7 +482,7 @@ int xmpi_count_mismatch(xmpi_comm* comm, const void* a, const void* b, size_t by
 int xmpi_checksum(xmpi_comm* comm, const void* buf, size_t bytes, uint64_t* sum);
 /* (bounce.go:133's floats.Equal with the differences spelled out)
  * stats[0] = max_i |a_i - b_i|, stats[1] = sum_i |b_i|, stats[2] = count of i with a NaN
- * mismatch; a, b of dtype F16/BF16/F32/F64; accumulated in double. */
+ * mismatch; a, b of dtype F16/BF16/F32/F64/F8E4M3/F8E5M2; accumulated in double. */
 int xmpi_diff_stats(xmpi_comm* comm, const void* a, const void* b, size_t count,
                     xmpi_dtype dtype, double stats[3]);
 /* (bounce.go:133 again, relative)  *max_rel = max_i |a_i - b_i| / |b_i| (0/0 = 0, x/0 = inf; inf if a NaN sits on one side only), in double.  With

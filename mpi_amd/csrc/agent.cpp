@@ -177,12 +177,20 @@ int agent_submit_ll(xmpi_comm* c, const void* send, void* recv, size_t bytes, in
   if (c->ll_agent_us <= 0 || !c->ll_cmd_dev || !c->dsync_ok || !c->dpage || c->size < 2 || c->size > kDsyncRanks || bytes == 0 ||
       bytes > kLLMaxPayload)
     return 0;
+  // (a reduction of an 8-bit float type is launched: the agent's kernel does not know the two types, and three bits do not name them)
+  if (dtype_is_f8(dtype) && (ll_coll == LL_ALLREDUCE || ll_coll == LL_REDUCE)) return 0;
   AgentLine line = ll_line(c);
   if (c->ll_agent_running && line.gone()) c->ll_agent_running = false;  // it said it went: started again below
   static_assert(XMPI_OP_COUNT <= 8, "an LL command names its operator in three bits (kernels.h): a ninth operator needs another layout");
   static_assert(kAgentLLConsecutiveShift - kAgentLLOpShift == 3, "... and these are the three");
+  // The dtype has three bits too, and XMPI_F8E4M3 / XMPI_F8E5M2 (7, 8) do not both fit: the field is written for the seven types the
+  // agent's folds know and is 0 for the 8-bit floats, which come here for bcast / allgather only (their reductions were declined
+  // above) -- copies of bytes, for which the agent never reads the field.  A type the agent is to FOLD needs a place in the field first.
+  static_assert(XMPI_BF16 < 8 && kAgentLLOpShift - kAgentLLDtypeShift == 3, "the seven dtypes the agent folds are named in three bits");
+  static_assert(XMPI_DTYPE_COUNT == 9, "a new dtype: decline its reductions above, or widen the field");
+  const int cmd_dtype = dtype_is_f8(dtype) ? 0 : dtype;
   const uint64_t meta = (uint64_t)(ll_coll & 3) | ((uint64_t)(root & 15) << kAgentLLRootShift) |
-                        ((uint64_t)(dtype & 7) << kAgentLLDtypeShift) | ((uint64_t)(op & 7) << kAgentLLOpShift) |
+                        ((uint64_t)(cmd_dtype & 7) << kAgentLLDtypeShift) | ((uint64_t)(op & 7) << kAgentLLOpShift) |
                         ((uint64_t)(consecutive ? 1 : 0) << kAgentLLConsecutiveShift);
   const uint64_t seq = line.post((uint64_t)(uintptr_t)send, (uint64_t)(uintptr_t)recv, meta, bytes);
   auto launch = [&](hipStream_t s) {

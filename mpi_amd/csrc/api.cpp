@@ -136,7 +136,8 @@ static int collective_on_host_meeting_ranks(xmpi_comm* c, int coll, int algo, in
   PlanParams pp;
   pp.coll = coll;
   // (XMPI_SUM_WIDE, reduce: staged AUTO picks the TREE for short messages -- partial sums in T; the one-hop table folds at the root)
-  pp.algo = (op == XMPI_SUM_WIDE && coll == COLL_REDUCE && algo == XMPI_ALGO_AUTO) ? (int)XMPI_ALGO_DIRECT : algo;
+  // (the same for every operator on the 8-bit floats: fold_only)
+  pp.algo = (fold_only(dtype, op) && coll == COLL_REDUCE && algo == XMPI_ALGO_AUTO) ? (int)XMPI_ALGO_DIRECT : algo;
   pp.size = c->size;
   pp.rank = c->rank;
   pp.root = root;
@@ -220,8 +221,12 @@ static int collective(xmpi_comm* c, int coll, int algo, int root, const void* se
   // travel between ranks in the 16-bit type, so no wide accumulator exists.  From the arguments alone: every rank answers alike,
   // before anything is announced or lent.
   op = normal_op(dtype, op);
-  if (op == XMPI_SUM_WIDE && coll_reduces(coll) && algo_stepped(algo)) {
-    set_last_error(std::string("XMPI_SUM_WIDE has no ") + algo_name(algo) + " schedule: ring, halving and tree pass partial sums between ranks in the 16-bit type (auto | zcopy | zpush | ll | direct)");
+  // The same for every reduction of XMPI_F8E4M3 / XMPI_F8E5M2, whatever the operator (comm.h fold_only).
+  if (fold_only(dtype, op) && coll_reduces(coll) && algo_stepped(algo)) {
+    if (dtype_is_f8(dtype))
+      set_last_error(std::string("a reduction of XMPI_F8E4M3 / XMPI_F8E5M2 has no ") + algo_name(algo) + " schedule: ring, halving and tree pass partial results between ranks in the 8-bit type (auto | zcopy | zpush | ll | direct)");
+    else
+      set_last_error(std::string("XMPI_SUM_WIDE has no ") + algo_name(algo) + " schedule: ring, halving and tree pass partial sums between ranks in the 16-bit type (auto | zcopy | zpush | ll | direct)");
     return XMPI_ERR_UNSUPPORTED;
   }
   // reduce-scatter and all-to-all: the schedules that exist for them, decided from the arguments alone (every rank answers alike)
@@ -304,6 +309,8 @@ size_t xmpi_dtype_size(xmpi_dtype dtype) {
     case XMPI_F32: return 4;
     case XMPI_F64: return 8;
     case XMPI_BF16: return 2;
+    case XMPI_F8E4M3: return 1;
+    case XMPI_F8E5M2: return 1;
     default: return 0;
   }
 }
@@ -776,8 +783,8 @@ int xmpi_allreduce_repeat(xmpi_comm* c, const void* sendbuf, void* recvbuf, size
   XMPI_ENTER(c);
   if (refuse_bitwise_on_float((int)dtype, (int)op)) return XMPI_ERR_ARG;
   if (op >= 0 && op < XMPI_OP_COUNT) op = (xmpi_op)normal_op((int)dtype, (int)op);
-  // (XMPI_SUM_WIDE on a stepped schedule: refused by collective() below, from the arguments alone)
-  const bool wide_stepped = op == XMPI_SUM_WIDE && algo_stepped(algo);
+  // (XMPI_SUM_WIDE, or an 8-bit float type, on a stepped schedule: refused by collective() below, from the arguments alone)
+  const bool wide_stepped = fold_only((int)dtype, (int)op) && algo_stepped(algo);
   // Ranks that meet on the device: the steps are ENQUEUED back to back on the communicator's stream and waited for
   // once -- what a stream-ordered caller does, and what the device rendezvous is for (no host round trip per
   // step).  Sampled launches carry their own events, read when the last step has been waited for.

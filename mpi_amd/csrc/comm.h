@@ -376,16 +376,24 @@ inline int use_device(const xmpi_comm* c) {
     ::xmpi::t_api_call = (c)->api_calls.fetch_add(1, std::memory_order_relaxed) + 1; \
   } while (0)
 // no-progress limit of a steady-state wait: XMPI_TIMEOUT_S, or for ever
-// XMPI_SUM_WIDE is XMPI_SUM for every type but the two 16-bit floats (include/xmpi.h): said once, at the C entry, before a route
-// or a call signature is formed -- a rank passing SUM_WIDE on f32 is in the same call as a rank passing SUM
-inline int normal_op(int dtype, int op) { return (op == XMPI_SUM_WIDE && dtype != XMPI_F16 && dtype != XMPI_BF16) ? (int)XMPI_SUM : op; }
+// XMPI_SUM_WIDE is XMPI_SUM for every type but the two 16-bit and the two 8-bit floats (include/xmpi.h): said once, at the C entry,
+// before a route or a call signature is formed -- a rank passing SUM_WIDE on f32 is in the same call as a rank passing SUM
+inline bool dtype_is_f8(int dtype) { return dtype == XMPI_F8E4M3 || dtype == XMPI_F8E5M2; }
+inline int normal_op(int dtype, int op) {
+  return (op == XMPI_SUM_WIDE && dtype != XMPI_F16 && dtype != XMPI_BF16 && !dtype_is_f8(dtype)) ? (int)XMPI_SUM : op;
+}
+// A reduction that exists only where all N contributions to an element meet in one lane (the fold family: launch.h with_fold_op):
+// XMPI_SUM_WIDE (after normal_op: f16 / bf16 and the 8-bit floats), and EVERY operator on XMPI_F8E4M3 / XMPI_F8E5M2.  The one
+// predicate behind the refusal of a stepped schedule a caller names, the fold a tuned table's stepped row turns into, and staged
+// AUTO reduce running DIRECT.  `op`: what normal_op returned.
+inline bool fold_only(int dtype, int op) { return op == XMPI_SUM_WIDE || dtype_is_f8(dtype); }
 // XMPI_BAND / XMPI_BOR / XMPI_BXOR are defined for XMPI_U8 / I32 / I64 (include/xmpi.h).  Asked at every entry that takes an operator,
-// beside normal_op: true = the operator is one of the three and the dtype one of the four float types -- xmpi_last_error now says
+// beside normal_op: true = the operator is one of the three and the dtype one of the six float types -- xmpi_last_error now says
 // so and the caller answers XMPI_ERR_ARG.  From the arguments alone, so every rank answers alike before anything is announced or
 // launched.  (An operator or a dtype that does not exist is not this function's to refuse: false.)
 inline bool op_is_bitwise(int op) { return op == XMPI_BAND || op == XMPI_BOR || op == XMPI_BXOR; }
 inline bool refuse_bitwise_on_float(int dtype, int op) {
-  if (!op_is_bitwise(op) || !(dtype == XMPI_F16 || dtype == XMPI_F32 || dtype == XMPI_F64 || dtype == XMPI_BF16)) return false;
+  if (!op_is_bitwise(op) || !(dtype == XMPI_F16 || dtype == XMPI_F32 || dtype == XMPI_F64 || dtype == XMPI_BF16 || dtype_is_f8(dtype))) return false;
   set_last_error("a bitwise operator (XMPI_BAND / XMPI_BOR / XMPI_BXOR) needs an integer type: XMPI_U8, XMPI_I32 or XMPI_I64");
   return true;
 }

@@ -111,8 +111,11 @@ static int dsync_ll(DsyncCall& call, const CollArgs& k, const void* sendbuf, voi
   // 2 processes; host slices 10.0 against 13.8; at 16 KiB it is a tie, 12.1 / 11.7, and beyond the launched kernel's many blocks
   // win) -- scripts/r04_agent_limit.sh
   const size_t agent_limit = (size_t)std::max<long>(0, c->agent_ll_bytes);
-  // (the agent knows the four collectives whose ranks all send the same line; reduce-scatter and all-to-all are launched)
-  if (blocking && !capturing && !coll_personal(coll) && call.lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
+  // (the agent knows the four collectives whose ranks all send the same line; reduce-scatter and all-to-all are launched -- and so is
+  // a REDUCTION of an 8-bit float type: the agent's kernel is not taught the two types, which keeps its registers as they were, and
+  // its command names a dtype in three bits)
+  const bool f8_fold = dtype_is_f8(k.dtype) && (coll == COLL_ALLREDUCE || coll == COLL_REDUCE);
+  if (blocking && !capturing && !coll_personal(coll) && !f8_fold && call.lent.empty() && c->agent_ll && unit <= agent_limit && !c->prof_on &&
       (quiet ||
        (idle(stream) && (!c->dsync_last_stream || c->dsync_last_stream == stream || idle(c->dsync_last_stream))))) {
     ++c->dsync_epoch;
@@ -352,7 +355,7 @@ int dsync_collective(xmpi_comm* c, int coll, int root, const void* sendbuf, void
   const bool capturing = call.capturing;
 
   // route: a refused call and an LL call end here
-  const DsyncRoute rt = dsync_route(c, coll, algo, k.unit, capturing, op == XMPI_SUM_WIDE && coll_reduces(coll));
+  const DsyncRoute rt = dsync_route(c, coll, algo, k.unit, capturing, fold_only(dtype, op) && coll_reduces(coll));
   if (rt.refused >= 0) return dsync_refuse(coll, rt.refused);
   if (rt.form == DsyncRoute::LL) return dsync_ll(call, k, sendbuf, recvbuf);
   RoctxRange range("xmpi:dsync %s algo=%s bytes=%zu epoch=%llu %s", coll_name(coll), algo_name(rt.algo), k.send_bytes,

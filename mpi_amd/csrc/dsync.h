@@ -64,7 +64,7 @@ inline uint64_t sig_fold(uint64_t h) { return std::max<uint64_t>(1, (h ^ (h >> 3
 
 // ---- dsync_plan.cpp.  Pure: from the communicator and the arguments only, the same answer on every rank
 int dsync_grid(const xmpi_comm* c, size_t packets_per_segment, int nseg, int unroll);
-DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool capturing, bool wide = false);  // wide: XMPI_SUM_WIDE on f16 / bf16
+DsyncRoute dsync_route(const xmpi_comm* c, int coll, int algo, size_t unit, bool capturing, bool wide = false);  // wide: a reduction of the fold family only (comm.h fold_only)
 uint64_t call_sig(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt);
 FoldPlan plan_for(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt);  // the fold family's plan of a call (not LL, not STEPPED)
 size_t plan_sched(const xmpi_comm* c, const CollArgs& k, const DsyncRoute& rt, const DsyncArgs& a, DsyncSchedArgs* out, int* gx_out);

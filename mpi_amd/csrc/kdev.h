@@ -24,9 +24,11 @@ namespace {
 constexpr int kBlock = 256;      // 4 waves: one per SIMD
 constexpr int kUnroll = 4;       // 16-byte packets per lane per operand in flight
 
-enum { DT_U8 = 0, DT_I32 = 1, DT_I64 = 2, DT_F16 = 3, DT_F32 = 4, DT_F64 = 5, DT_BF16 = 6 };
-// OP_SUM_WIDE (XMPI_SUM_WIDE): _Float16 / bf16_t only, and only in the kernels that see all N contributions to an element in one
-// lane (FoldAcc below); the launchers hand it to nothing else (launch.h with_fold_op)
+enum { DT_U8 = 0, DT_I32 = 1, DT_I64 = 2, DT_F16 = 3, DT_F32 = 4, DT_F64 = 5, DT_BF16 = 6, DT_F8E4M3 = 7, DT_F8E5M2 = 8 };
+// OP_SUM_WIDE (XMPI_SUM_WIDE): _Float16 / bf16_t / f8e4m3_t / f8e5m2_t only, and only in the kernels that see all N contributions to
+// an element in one lane (FoldAcc below); the launchers hand it to nothing else (launch.h with_fold_op)
+// The two 8-bit float types exist in those kernels only, under every operator: the stepped kernels and reduce2* pass partial results
+// between ranks in T, and two or three mantissa bits are not something to pass round a ring (launch.h keeps them out)
 // OP_BAND / OP_BOR / OP_BXOR (XMPI_BAND / _BOR / _BXOR): uint8_t, int32_t and int64_t only, in every kernel that has an operator
 // (launch.h with_op hands them on for those three types and for no other)
 enum { OP_SUM = 0, OP_PROD = 1, OP_MIN = 2, OP_MAX = 3, OP_SUM_WIDE = 4, OP_BAND = 5, OP_BOR = 6, OP_BXOR = 7 };
@@ -36,6 +38,16 @@ constexpr bool kBitOp = OP == OP_BAND || OP == OP_BOR || OP == OP_BXOR;
 struct bf16_t {
   uint16_t bits;
 };
+// OCP 8-bit floating point v1.0.  E4M3: S.EEEE.MMM, bias 7, no infinities, S.1111.111 is NaN, largest finite 448 (0x7E), smallest
+// subnormal 2^-9.  E5M2: S.EEEEE.MM, bias 15, IEEE-like: 0x7C +-inf, 0x7D..0x7F NaN, largest finite 57344 (0x7B), smallest subnormal 2^-16.
+struct f8e4m3_t {
+  uint8_t bits;
+};
+struct f8e5m2_t {
+  uint8_t bits;
+};
+template <typename T>
+constexpr bool kF8Elem = __is_same(T, f8e4m3_t) || __is_same(T, f8e5m2_t);
 
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 // 16-byte packet: a native vector (not HIP's pack_t struct) so it always lives in 4 VGPRs
@@ -85,6 +97,123 @@ __device__ __forceinline__ bf16_t combine_bf16(bf16_t a, bf16_t b) {
   else if constexpr (OP == OP_MAX) return (x < y) ? b : a;
 }
 
+// ---- the 8-bit floats: f32(x) is exact; narrow(f) rounds to nearest, ties to even, with gradual underflow, and SATURATES -------------
+// A NaN gives a NaN of the type (which one is not specified); +-inf gives +-inf (E5M2; E4M3 has none and no fold reaches one); any
+// other value whose rounded magnitude exceeds the largest finite one becomes +-448 / +-57344 (the default of HIP's __hip_fp8 types): a
+// sum of finite inputs never turns into inf or NaN.  Written once in plain C++ -- the definition, what the host pass and tests/devsim
+// compile, and what tests/f8_ref.py restates -- and, on gfx950, as the packed conversion instructions further down, which are
+// held to it bit for bit by the tests on the card.
+template <bool E5>
+__device__ __forceinline__ float f8_to_f32_soft(uint8_t b) {
+  constexpr int MB = E5 ? 2 : 3, BIAS = E5 ? 15 : 7;
+  const uint32_t sign = (uint32_t)(b & 0x80u) << 24, e = (uint32_t)(b & 0x7Fu) >> MB, m = b & ((1u << MB) - 1u);
+  if constexpr (E5) {
+    if (e == 31u) return __uint_as_float(sign | 0x7F800000u | (m << 21));  // +-inf, NaN
+  } else {
+    if ((b & 0x7Fu) == 0x7Fu) return __uint_as_float(sign | 0x7FC00000u);
+  }
+  if (e == 0u) return __uint_as_float(sign | __float_as_uint((float)m * (E5 ? 0x1p-16f : 0x1p-9f)));  // +-0 and the subnormals
+  return __uint_as_float(sign | ((e + 127u - (uint32_t)BIAS) << 23) | (m << (23 - MB)));
+}
+template <bool E5>
+__device__ __forceinline__ uint8_t f32_to_f8_soft(float f) {
+  constexpr int MB = E5 ? 2 : 3, BIAS = E5 ? 15 : 7, EMIN = 1 - BIAS;
+  constexpr uint32_t MAXFIN = E5 ? 0x7Bu : 0x7Eu;
+  const uint32_t u = __float_as_uint(f), a = u & 0x7FFFFFFFu;
+  const uint8_t sign = (uint8_t)((u >> 24) & 0x80u);
+  if (a > 0x7F800000u) return (uint8_t)(sign | 0x7Fu);                     // NaN
+  if (a == 0x7F800000u) return (uint8_t)(sign | (E5 ? 0x7Cu : MAXFIN));    // inf (E4M3: never reached; saturates)
+  const int e = (int)(a >> 23) - 127;
+  const uint32_t sig = (a & 0x7FFFFFu) | 0x800000u;  // 1.m, 24 bits (an f32 subnormal has e = -127: far below half the smallest subnormal)
+  uint32_t q = 0;
+  // the bits below the type's last place: `sh` of them -- 23 - MB for a normal result, one more per binade below the smallest normal
+  const int sh = 23 - MB + (e >= EMIN ? 0 : EMIN - e);
+  if (sh <= 24) {
+    q = sig >> sh;
+    const uint32_t rem = sig & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    if (rem > half || (rem == half && (q & 1u))) q++;
+    // normal: the leading 1 of q counts as exponent 1 + ...; a carry out of the mantissa runs into the exponent field as it should
+    if (e >= EMIN) q += (uint32_t)(e + BIAS - 1) << MB;
+  }
+  if (q > MAXFIN) q = MAXFIN;  // saturate (E5M2: this is also what keeps a rounded 0x7C from reading as inf)
+  return (uint8_t)(sign | q);
+}
+template <typename T>
+__device__ __forceinline__ float f8_to_f32(T v) {
+  static_assert(kF8Elem<T>, "f8e4m3_t or f8e5m2_t");
+#if defined(__gfx950__)
+  if constexpr (__is_same(T, f8e4m3_t)) return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0);
+  else return __builtin_amdgcn_cvt_f32_bf8((int)v.bits, 0);
+#else
+  return f8_to_f32_soft<__is_same(T, f8e5m2_t)>(v.bits);
+#endif
+}
+#if defined(__gfx950__)
+// the saturation, before the instruction: it is not relied on for anything past the largest finite value (NaN and inf pass as they are)
+template <typename T>
+__device__ __forceinline__ float f8_clamp(float f) {
+  constexpr float M = __is_same(T, f8e4m3_t) ? 448.0f : 57344.0f;
+  return __builtin_amdgcn_classf(f, 0x207) ? f : __builtin_amdgcn_fmed3f(f, M, -M);  // 0x207: sNaN | qNaN | -inf | +inf
+}
+// two floats -> the low (HI = false) or high half of `old`
+template <typename T, bool HI>
+__device__ __forceinline__ int f8_pack2(float a, float b, int old) {
+  if constexpr (__is_same(T, f8e4m3_t)) return __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp<T>(a), f8_clamp<T>(b), old, HI);
+  else return __builtin_amdgcn_cvt_pk_bf8_f32(f8_clamp<T>(a), f8_clamp<T>(b), old, HI);
+}
+#endif
+template <typename T>
+__device__ __forceinline__ T f32_to_f8(float f) {
+  static_assert(kF8Elem<T>, "f8e4m3_t or f8e5m2_t");
+#if defined(__gfx950__)
+  return T{(uint8_t)f8_pack2<T, false>(f, f, 0)};
+#else
+  return T{f32_to_f8_soft<__is_same(T, f8e5m2_t)>(f)};
+#endif
+}
+// the 4 elements of a 32-bit word <-> 4 floats: v_cvt_pk_f32_fp8 / _bf8 (two elements per instruction, the half word selected) and
+// v_cvt_pk_fp8_f32 / _bf8_f32 on gfx950
+template <typename T>
+__device__ __forceinline__ void f8_widen4(uint32_t w, float* f) {
+#if defined(__gfx950__)
+  typedef float float2_t __attribute__((ext_vector_type(2)));
+  float2_t lo, hi;
+  if constexpr (__is_same(T, f8e4m3_t)) {
+    lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  } else {
+    lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+    hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
+  }
+  f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+#else
+#pragma unroll
+  for (int i = 0; i < 4; i++) f[i] = f8_to_f32_soft<__is_same(T, f8e5m2_t)>((uint8_t)(w >> (8 * i)));
+#endif
+}
+template <typename T>
+__device__ __forceinline__ uint32_t f8_narrow4(const float* f) {
+#if defined(__gfx950__)
+  return (uint32_t)f8_pack2<T, true>(f[2], f[3], f8_pack2<T, false>(f[0], f[1], 0));
+#else
+  uint32_t w = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) w |= (uint32_t)f32_to_f8_soft<__is_same(T, f8e5m2_t)>(f[i]) << (8 * i);
+  return w;
+#endif
+}
+
+// min / max compare the widened values with combine_bf16's expressions and return the chosen operand's own byte
+template <typename T, int OP>
+__device__ __forceinline__ T combine_f8(T a, T b) {
+  static_assert(OP >= OP_SUM && OP <= OP_MAX, "an 8-bit float has the four arithmetic operators (the bitwise ones are for integer types)");
+  const float x = f8_to_f32(a), y = f8_to_f32(b);
+  if constexpr (OP == OP_SUM) return f32_to_f8<T>(x + y);
+  else if constexpr (OP == OP_PROD) return f32_to_f8<T>(x * y);
+  else if constexpr (OP == OP_MIN) return (y < x) ? b : a;
+  else if constexpr (OP == OP_MAX) return (x < y) ? b : a;
+}
+
 // wrapping integer arithmetic (Go semantics) without signed-overflow UB
 template <int OP>
 __device__ __forceinline__ int32_t combine_i32(int32_t a, int32_t b) {
@@ -101,7 +230,8 @@ __device__ __forceinline__ int64_t combine_i64(int64_t a, int64_t b) {
 
 template <typename T, int OP>
 __device__ __forceinline__ T combine_any(T a, T b) {
-  if constexpr (sizeof(T) == 2 && !__is_same(T, _Float16)) return combine_bf16<OP>(a, b);
+  if constexpr (kF8Elem<T>) return combine_f8<T, OP>(a, b);
+  else if constexpr (sizeof(T) == 2 && !__is_same(T, _Float16)) return combine_bf16<OP>(a, b);
   else if constexpr (__is_same(T, int32_t)) return combine_i32<OP>(a, b);
   else if constexpr (__is_same(T, int64_t)) return combine_i64<OP>(a, b);
   else if constexpr (__is_same(T, uint8_t)) {
@@ -109,6 +239,51 @@ __device__ __forceinline__ T combine_any(T a, T b) {
     else if constexpr (OP == OP_PROD) return (uint8_t)(a * b);
     else return combine<uint8_t, OP>(a, b);
   } else return combine<T, OP>(a, b);
+}
+
+// ---- a word of 8-bit floats (a 16-byte packet: 16 elements; the 8 payload bytes of an LL line: 8) ------------------------------
+// Both operands are widened ONCE with the packed conversions (a packet: 8 instructions each), combined as floats and narrowed with
+// the packed conversions -- not sixteen scalar round trips.  min / max pick whole bytes of the operands by the widened comparison.
+template <typename T, typename W>
+__device__ __forceinline__ void f8_widen_word(W w, float (&f)[sizeof(W)]) {
+  union { W u; uint32_t d[sizeof(W) / 4]; } x;
+  x.u = w;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(W) / 4); i++) f8_widen4<T>(x.d[i], &f[4 * i]);
+}
+template <typename T, typename W>
+__device__ __forceinline__ W f8_narrow_word(const float (&f)[sizeof(W)]) {
+  union { W u; uint32_t d[sizeof(W) / 4]; } r;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(W) / 4); i++) r.d[i] = f8_narrow4<T>(&f[4 * i]);
+  return r.u;
+}
+template <typename T, int OP, typename W>
+__device__ __forceinline__ W combine_f8_word(W a, W b) {
+  static_assert(OP >= OP_SUM && OP <= OP_MAX, "an 8-bit float has the four arithmetic operators");
+  constexpr int N = sizeof(W);
+  float x[N], y[N];
+  f8_widen_word<T, W>(a, x);
+  f8_widen_word<T, W>(b, y);
+  if constexpr (OP == OP_SUM || OP == OP_PROD) {
+#pragma unroll
+    for (int i = 0; i < N; i++) x[i] = (OP == OP_SUM) ? (x[i] + y[i]) : (x[i] * y[i]);
+    return f8_narrow_word<T, W>(x);
+  } else {
+    union { W u; uint32_t d[N / 4]; } p, q, r;
+    p.u = a; q.u = b;
+#pragma unroll
+    for (int i = 0; i < N / 4; i++) {
+      uint32_t take_b = 0;  // 0xFF in every byte whose element comes from b
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const bool t = (OP == OP_MIN) ? (y[4 * i + k] < x[4 * i + k]) : (x[4 * i + k] < y[4 * i + k]);
+        take_b |= t ? (0xFFu << (8 * k)) : 0u;
+      }
+      r.d[i] = (q.d[i] & take_b) | (p.d[i] & ~take_b);
+    }
+    return r.u;
+  }
 }
 
 // ---- 16-byte packet combine ------------------------------------------------------------------
@@ -126,6 +301,8 @@ __device__ __forceinline__ pack_t combine16(pack_t a, pack_t b) {
 #pragma unroll
     for (int i = 0; i < 4; i++) r.h[i] = (OP == OP_SUM) ? (x.h[i] + y.h[i]) : (x.h[i] * y.h[i]);
     return r.u;
+  } else if constexpr (kF8Elem<T>) {
+    return combine_f8_word<T, OP, pack_t>(a, b);
   } else {
     union { pack_t u; T e[N]; } x, y, r;
     x.u = a; y.u = b;
@@ -141,6 +318,8 @@ __device__ __forceinline__ uint64_t combine8(uint64_t a, uint64_t b) {
   if constexpr (kBitOp<OP>) {
     static_assert(kIntegerElem<T>, "a bitwise operator is never instantiated with a floating-point type or bf16_t (launch.h with_op)");
     return bitop<OP>(a, b);
+  } else if constexpr (kF8Elem<T>) {
+    return combine_f8_word<T, OP, uint64_t>(a, b);
   } else {
     constexpr int N = 8 / sizeof(T);
     union {
@@ -158,48 +337,60 @@ __device__ __forceinline__ uint64_t combine8(uint64_t a, uint64_t b) {
 // ---- the accumulator of a fold: first source, N-1 times add(), result() ----------------------------------------------------
 // W is what a lane holds of every source: a 16-byte packet (pack_t), the 8 payload bytes of an LL line (uint64_t) or one element (T).
 // Every operator but OP_SUM_WIDE accumulates in W itself -- combine16 / combine8 / combine_any per source, one rounding each, which
-// is "bit-identical to a host sum in rank order".  OP_SUM_WIDE (_Float16, bf16_t) holds the sizeof(W) / 2 elements as floats:
+// is "bit-identical to a host sum in rank order" (the 8-bit floats: acc = narrow(f32(acc) op f32(x)), a packet widened and narrowed by
+// the packed conversions, the accumulator in its four VGPRs between sources).  OP_SUM_WIDE (_Float16, bf16_t, f8e4m3_t, f8e5m2_t)
+// holds the sizeof(W) / sizeof(T) elements as floats:
 //   narrow( ((f32(x0) + f32(x1)) + f32(x2)) + ... )      f32() exact, IEEE f32 additions in source order, narrow() ONCE --
-// bf16: f32_to_bf16 above (round to nearest even, its NaN rule); f16: the conversion (_Float16)f, round to nearest even.
-// Plain C++ conversions: tests/devsim compiles this for the host.
+// bf16: f32_to_bf16 above (round to nearest even, its NaN rule); f16: the conversion (_Float16)f, round to nearest even; the 8-bit
+// floats: f32_to_f8 (nearest even, saturating).  Plain C++ conversions wherever this is not compiled for gfx950: tests/devsim
+// compiles it for the host.
+// (the 8-bit floats: f8_to_f32 / f32_to_f8 above -- a word of them by the packed conversions, an element alone by itself)
 template <typename T>
 __device__ __forceinline__ float widen1(T v) {
-  static_assert(sizeof(T) == 2, "_Float16 or bf16_t");
-  if constexpr (__is_same(T, _Float16)) return (float)v;
+  static_assert(sizeof(T) < 4, "_Float16, bf16_t, f8e4m3_t or f8e5m2_t");
+  if constexpr (kF8Elem<T>) return f8_to_f32(v);
+  else if constexpr (__is_same(T, _Float16)) return (float)v;
   else return bf16_to_f32(v.bits);
 }
 template <typename T>
 __device__ __forceinline__ T narrow1(float f) {
-  static_assert(sizeof(T) == 2, "_Float16 or bf16_t");
-  if constexpr (__is_same(T, _Float16)) return (_Float16)f;
+  static_assert(sizeof(T) < 4, "_Float16, bf16_t, f8e4m3_t or f8e5m2_t");
+  if constexpr (kF8Elem<T>) return f32_to_f8<T>(f);
+  else if constexpr (__is_same(T, _Float16)) return (_Float16)f;
   else return bf16_t{f32_to_bf16(f)};
 }
 template <typename T, typename W>
-__device__ __forceinline__ void widen_word(W w, float (&f)[sizeof(W) / 2]) {
-  union { W u; T e[sizeof(W) / 2]; } x;
-  x.u = w;
+__device__ __forceinline__ void widen_word(W w, float (&f)[sizeof(W) / sizeof(T)]) {
+  if constexpr (kF8Elem<T> && sizeof(W) >= 4) f8_widen_word<T, W>(w, f);
+  else {
+    union { W u; T e[sizeof(W) / sizeof(T)]; } x;
+    x.u = w;
 #pragma unroll
-  for (int i = 0; i < (int)(sizeof(W) / 2); i++) f[i] = widen1<T>(x.e[i]);
+    for (int i = 0; i < (int)(sizeof(W) / sizeof(T)); i++) f[i] = widen1<T>(x.e[i]);
+  }
 }
 template <typename T, typename W>
-__device__ __forceinline__ W narrow_word(const float (&f)[sizeof(W) / 2]) {
-  union { W u; T e[sizeof(W) / 2]; } r;
+__device__ __forceinline__ W narrow_word(const float (&f)[sizeof(W) / sizeof(T)]) {
+  if constexpr (kF8Elem<T> && sizeof(W) >= 4) return f8_narrow_word<T, W>(f);
+  else {
+    union { W u; T e[sizeof(W) / sizeof(T)]; } r;
 #pragma unroll
-  for (int i = 0; i < (int)(sizeof(W) / 2); i++) r.e[i] = narrow1<T>(f[i]);
-  return r.u;
+    for (int i = 0; i < (int)(sizeof(W) / sizeof(T)); i++) r.e[i] = narrow1<T>(f[i]);
+    return r.u;
+  }
 }
-// a 16-byte packet of 8 halves / bfloat16s <-> 8 floats
+// a 16-byte packet of 8 halves / bfloat16s or 16 8-bit floats <-> as many floats
 template <typename T>
-__device__ __forceinline__ void widen16(pack_t p, float (&f)[8]) { widen_word<T, pack_t>(p, f); }
+__device__ __forceinline__ void widen16(pack_t p, float (&f)[16 / sizeof(T)]) { widen_word<T, pack_t>(p, f); }
 template <typename T>
-__device__ __forceinline__ pack_t narrow16(const float (&f)[8]) { return narrow_word<T, pack_t>(f); }
+__device__ __forceinline__ pack_t narrow16(const float (&f)[16 / sizeof(T)]) { return narrow_word<T, pack_t>(f); }
 
 template <typename T, int OP>
-constexpr bool kWideFold = OP == OP_SUM_WIDE && (__is_same(T, _Float16) || __is_same(T, bf16_t));
+constexpr bool kWideFold = OP == OP_SUM_WIDE && (__is_same(T, _Float16) || __is_same(T, bf16_t) || kF8Elem<T>);
 
 template <typename T, int OP, typename W, bool WIDE = kWideFold<T, OP>>
 struct FoldAcc {
-  static_assert(OP != OP_SUM_WIDE, "OP_SUM_WIDE is OP_SUM for every type but _Float16 / bf16_t: the launcher says so (with_fold_op)");
+  static_assert(OP != OP_SUM_WIDE, "OP_SUM_WIDE is OP_SUM for every type but _Float16 / bf16_t / the 8-bit floats: the launcher says so (with_fold_op)");
   W v;
   __device__ __forceinline__ explicit FoldAcc(W first) : v(first) {}
   __device__ __forceinline__ void add(W x) {
@@ -211,7 +402,7 @@ struct FoldAcc {
 };
 template <typename T, int OP, typename W>
 struct FoldAcc<T, OP, W, true> {
-  static constexpr int N = sizeof(W) / 2;
+  static constexpr int N = sizeof(W) / sizeof(T);  // an element narrower than f32: 8 or 16 of a packet, 4 or 8 of an LL line, 1
   float f[N];
   __device__ __forceinline__ explicit FoldAcc(W first) { widen_word<T, W>(first, f); }
   __device__ __forceinline__ void add(W x) {

@@ -496,7 +496,8 @@ __global__ __launch_bounds__(kBlock) void checksum_kernel(const uint8_t* buf, si
 
 template <typename T>
 __device__ __forceinline__ double as_double(T v) {
-  if constexpr (sizeof(T) == 2 && !__is_same(T, _Float16)) return (double)bf16_to_f32(v.bits);
+  if constexpr (kF8Elem<T>) return (double)f8_to_f32(v);
+  else if constexpr (sizeof(T) == 2 && !__is_same(T, _Float16)) return (double)bf16_to_f32(v.bits);
   else return (double)v;
 }
 
@@ -938,9 +939,14 @@ hipError_t launch_reduce2(void* dst, const void* a, const void* b, size_t count,
     record_events(es, ee, s);
     return hipSuccess;
   }
+  if (dtype == DT_F8E4M3 || dtype == DT_F8E5M2) {  // the 8-bit floats exist in the fold family only: two sources, folded
+    const void* two[2] = {a, b};
+    return launch_reduce_n(dst, two, 2, count, dtype, op, s, es, ee);
+  }
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op<T>(op, [&](auto o) {
+    if constexpr (kF8Elem<T>) return hipErrorInvalidValue;  // never reached (handed on above): it keeps reduce2* from being instantiated for them
+    else return with_op<T>(op, [&](auto o) {
       constexpr int OP = decltype(o)::value;
       if (aligned16(dst) && aligned16(a) && aligned16(b)) {
         const size_t npack = count / (16 / sizeof(T));
@@ -1028,7 +1034,8 @@ hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void*
     fused = fused || q.dst2[i] != nullptr || dst[i] == nullptr;
     ok = ok && aligned16(dst[i]) && aligned16(q.dst2[i]) && aligned16(a[i]) && aligned16(b[i]);
   }
-  if (!ok || (n == 1 && !fused) || maxc == 0)  // odd alignment / nothing to fuse: plain launches
+  const bool f8 = dtype == DT_F8E4M3 || dtype == DT_F8E5M2;  // (no reduce2 kernel exists for them: launch_reduce2 folds each segment)
+  if (!ok || (n == 1 && !fused) || maxc == 0 || f8)  // odd alignment / nothing to fuse: plain launches
     // The local destination may alias an operand (in-place ring step: dst == a): the forwarded copy is computed FIRST, from the
     // untouched operands, and the aliasing store comes last.  A segment without elements or without a destination launches nothing.
     return launch_per_dest(
@@ -1036,7 +1043,8 @@ hipError_t launch_reduce2_batch(void* const* dst, void* const* dst2, const void*
         [&](int i, void* d, hipEvent_t e0, hipEvent_t e1) { return launch_reduce2(d, a[i], b[i], counts[i], dtype, op, s, e0, e1); });
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op<T>(op, [&](auto o) {
+    if constexpr (kF8Elem<T>) return hipErrorInvalidValue;  // never reached (`f8` took the plain launches above): no instantiation for them
+    else return with_op<T>(op, [&](auto o) {
       const dim3 grid(batch_grid_x(maxc / (16 / sizeof(T)), n), n);
       return with_mode012(kernel_mode_for(3 * total * sizeof(T)), [&](auto m) {
         XMPI_LAUNCH((reduce2_batch_kernel<T, decltype(o)::value, decltype(m)::value>), grid, dim3(kBlock), s, es, ee, q);

@@ -76,12 +76,16 @@ hipError_t with_dtype(int dtype, F&& f) {
     case DT_F32: return f(type_tag<float>{});
     case DT_F64: return f(type_tag<double>{});
     case DT_BF16: return f(type_tag<bf16_t>{});
+    case DT_F8E4M3: return f(type_tag<f8e4m3_t>{});
+    case DT_F8E5M2: return f(type_tag<f8e5m2_t>{});
     default: return hipErrorInvalidValue;
   }
 }
 
 // The operators of every kernel that has one: the four arithmetic ones for every T, and the three bitwise ones for the integer
 // types -- for any other T they answer hipErrorInvalidValue and nothing is instantiated (kdev.h would refuse to compile it).
+// The two 8-bit float types exist in the fold family only (with_fold_op): a launcher of anything else -- the stepped kernels,
+// reduce2* -- keeps them out with `if constexpr (kF8Elem<T>)` in front of this, so nothing of theirs is instantiated for them.
 template <typename T, typename F>
 hipError_t with_op(int op, F&& f) {
   switch (op) {
@@ -103,12 +107,12 @@ hipError_t with_op(int op, F&& f) {
 }
 
 // The fold family's operators (kernels whose lane sees every contribution to an element: reduce_n*, dsync_fold, dsync_body, the LL
-// folds): those of with_op and OP_SUM_WIDE -- handed through for the two 16-bit float types, OP_SUM for every other T, whose sum
-// it is.  A launcher of anything else (the stepped kernels, reduce2*) keeps to with_op and answers hipErrorInvalidValue.
+// folds): those of with_op and OP_SUM_WIDE -- handed through for the two 16-bit and the two 8-bit float types, OP_SUM for every
+// other T, whose sum it is.  A launcher of anything else (the stepped kernels, reduce2*) keeps to with_op and answers hipErrorInvalidValue.
 template <typename T, typename F>
 hipError_t with_fold_op(int op, F&& f) {
   if (op != OP_SUM_WIDE) return with_op<T>(op, f);
-  if constexpr (std::is_same_v<T, _Float16> || std::is_same_v<T, bf16_t>) return f(int_tag<OP_SUM_WIDE>{});
+  if constexpr (std::is_same_v<T, _Float16> || std::is_same_v<T, bf16_t> || kF8Elem<T>) return f(int_tag<OP_SUM_WIDE>{});
   else return f(int_tag<OP_SUM>{});
 }
 

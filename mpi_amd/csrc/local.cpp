@@ -182,7 +182,7 @@ int xmpi_checksum(xmpi_comm* c, const void* buf, size_t bytes, uint64_t* out) {
 int xmpi_diff_stats(xmpi_comm* c, const void* a, const void* b, size_t count, xmpi_dtype dtype, double stats[3]) {
   XMPI_ENTER(c);
   if (!stats) return XMPI_ERR_ARG;
-  if (dtype != XMPI_F16 && dtype != XMPI_BF16 && dtype != XMPI_F32 && dtype != XMPI_F64) return XMPI_ERR_ARG;
+  if (dtype != XMPI_F16 && dtype != XMPI_BF16 && dtype != XMPI_F32 && dtype != XMPI_F64 && !dtype_is_f8(dtype)) return XMPI_ERR_ARG;
   std::lock_guard<std::mutex> g(c->coll_mu);
   hipStream_t s = c->local_stream;
   uint64_t w[4] = {0, 0, 0, 0};
@@ -199,7 +199,7 @@ int xmpi_diff_stats(xmpi_comm* c, const void* a, const void* b, size_t count, xm
 int xmpi_diff_rel(xmpi_comm* c, const void* a, const void* b, size_t count, xmpi_dtype dtype, double* max_rel) {
   XMPI_ENTER(c);
   if (!max_rel) return XMPI_ERR_ARG;
-  if (dtype != XMPI_F16 && dtype != XMPI_BF16 && dtype != XMPI_F32 && dtype != XMPI_F64) return XMPI_ERR_ARG;
+  if (dtype != XMPI_F16 && dtype != XMPI_BF16 && dtype != XMPI_F32 && dtype != XMPI_F64 && !dtype_is_f8(dtype)) return XMPI_ERR_ARG;
   std::lock_guard<std::mutex> g(c->coll_mu);
   hipStream_t s = c->local_stream;
   uint64_t w[4] = {0, 0, 0, 0};

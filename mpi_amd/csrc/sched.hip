@@ -795,7 +795,8 @@ hipError_t launch_dsync_sched(const DsyncSchedArgs& a, int dtype, int op, int gr
   const bool moves_only = a.sched == SCHED_RING_ALLGATHER || a.sched == SCHED_TREE_BCAST;  // bytes, whatever the dtype: one kernel
   return with_dtype(moves_only ? (int)DT_U8 : dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return with_op<T>(moves_only ? (int)OP_SUM : op, [&](auto o) {
+    if constexpr (kF8Elem<T>) return hipErrorInvalidValue;  // (a stepped REDUCTION of an 8-bit float type: api.cpp refuses it first)
+    else return with_op<T>(moves_only ? (int)OP_SUM : op, [&](auto o) {
       XMPI_LAUNCH((dsync_sched_kernel<T, decltype(o)::value>), grid, dim3(kBlock), s, es, ee, a);
       return hipGetLastError();
     });

@@ -15,8 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxmpi.so")
 
 # enums of include/xmpi.h
-U8, I32, I64, F16, F32, F64, BF16 = range(7)
-SUM, PROD, MIN, MAX, SUM_WIDE = range(5)  # SUM_WIDE: f16 / bf16 accumulated in f32, rounded once (SUM for every other dtype)
+U8, I32, I64, F16, F32, F64, BF16, F8E4M3, F8E5M2 = range(9)  # F8E4M3 / F8E5M2: the OCP 8-bit floats (torch.float8_e4m3fn / float8_e5m2)
+SUM, PROD, MIN, MAX, SUM_WIDE = range(5)  # SUM_WIDE: f16 / bf16 / the 8-bit floats accumulated in f32, rounded once (SUM for every other dtype)
 BAND, BOR, BXOR = 5, 6, 7  # bitwise AND / OR / XOR: U8, I32 and I64 only (a float dtype is XMPI_ERR_ARG)
 ALGO_AUTO, ALGO_RING, ALGO_RHD, ALGO_DIRECT, ALGO_TREE, ALGO_ZCOPY, ALGO_ZPUSH, ALGO_LL, ALGO_RING_PUSH, ALGO_RHD_PUSH, ALGO_TREE_PUSH = range(11)
 COLL_ALLREDUCE, COLL_ALLGATHER, COLL_BCAST, COLL_REDUCE, COLL_REDUCE_SCATTER, COLL_ALLTOALL = range(6)
@@ -27,10 +27,10 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_BOOTSTRAP, ERR_TIMEOUT, ERR_TAG_EXISTS, ERR_TRUNCATE = -1, -2, -3, -4, -5, -6
 ERR_NOMEM, ERR_STATE, ERR_UNSUPPORTED, ERR_NOGPU, ERR_PEER = -7, -8, -9, -10, -11
 
-DTYPE_SIZE = {U8: 1, I32: 4, I64: 8, F16: 2, F32: 4, F64: 8, BF16: 2}
+DTYPE_SIZE = {U8: 1, I32: 4, I64: 8, F16: 2, F32: 4, F64: 8, BF16: 2, F8E4M3: 1, F8E5M2: 1}
 NUMPY_DTYPE = {U8: np.uint8, I32: np.int32, I64: np.int64, F16: np.float16, F32: np.float32, F64: np.float64,
-               BF16: np.uint16}  # bf16 travels as raw bit patterns
-DTYPE_NAME = {U8: "u8", I32: "i32", I64: "i64", F16: "f16", F32: "f32", F64: "f64", BF16: "bf16"}
+               BF16: np.uint16, F8E4M3: np.uint8, F8E5M2: np.uint8}  # bf16 and the 8-bit floats travel as raw bit patterns
+DTYPE_NAME = {U8: "u8", I32: "i32", I64: "i64", F16: "f16", F32: "f32", F64: "f64", BF16: "bf16", F8E4M3: "f8e4m3", F8E5M2: "f8e5m2"}
 
 # every symbol include/xmpi.h declares: (name, restype, argtypes)
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_long, C.c_size_t
